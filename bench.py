@@ -2,7 +2,7 @@
 """Headline benchmark: frames/s of the res101 image Faster R-CNN forward at 1000x600 (BASELINE.json
 configs[1]) on N MI355X GPUs, one process per GPU, one frame per GPU per step.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,8 +10,12 @@ A step = one synthetic frame per rank through the whole hot path (channel pad ->
 proposal sort/NMS -> RoIAlign -> layer4 on 300 RoIs -> detection tail -> per-class filter with the
 max_dets cut), replayed as one hipGraph, followed (N > 1) by the RCCL all-gather of the fixed-size
 detection records (the eval collate).  Frames are resident in HBM before the timed region starts.
-Rank 0 prints ONE JSON line; `roofline` is for the dominant kernel (the fp32-MFMA implicit-GEMM conv),
-`cpu_baseline` times the CPU oracle on a bounded sample of the same workload on this box's host cores.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly --steps steps and reports them;
+--dump-outputs DIR writes the detections of the last timed step as .npy files.  --full adds everything else:
+the host-upload leg, the bit-for-bit check of every timed record against the eager path, `roofline` for the
+dominant kernel (the fp32-MFMA implicit-GEMM conv) and the RoIAlign / NMS kernels, the drop-in legs,
+`cpu_baseline` (the CPU oracle on a bounded sample of the same workload on this box's host cores), the mAP
+delta and BASELINE configs[2] / configs[3].
 """
 import argparse
 import json
@@ -33,7 +37,7 @@ WEIGHT_SEED, BN_MODE = 3, "tame"     # cfg.RNG_SEED; see DESIGN.md "workload" fo
 MFMA_F32_PEAK_TFLOPS = 157.3         # MI355X_MICROARCH.md: dense fp32 matrix peak
 HBM_PEAK_GBS = 8000.0
 REFERENCE_ORDER_FLOPS = 628.4e9          # the frame's convolutions in the reference's order of operations
-MIN_TIMED_S = 1.0                    # repeat the --steps region until about this much timed work exists
+MIN_TIMED_S = 1.0                    # --regions 0: repeat the --steps region until about this much timed work exists
 # Committed rocprofv3 PMC passes (counters cannot be collected inside the timed run: one counter per pass, serialised
 # dispatches).  They were collected with the plan table PLANS_FILE; by default this run LOADS that table instead of re-tuning,
 # so the kernels it times are the kernels the passes measured (roofline.from_profiles.plans_match says so in the line).
@@ -515,8 +519,13 @@ def parse_args(argv=None):
                     "coprime with --streams)")
     ap.add_argument("--gather-every", type=int, default=8, help="frames per eval-collate block: one all-gather + one "
                     "device->host copy per block, on a dedicated stream")
-    ap.add_argument("--regions", type=int, default=0, help="timed repetitions of the --steps region (0 = until ~1 s is timed)")
-    ap.add_argument("--no-upload", action="store_true", help="skip the extra region that uploads every frame inside the step")
+    ap.add_argument("--regions", type=int, default=1, help="timed repetitions of the --steps region, the median is reported "
+                    "(default 1: exactly --steps timed steps; 0 = until ~1 s is timed)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run the other legs: host upload, verification of "
+                    "the timed records, rooflines, drop-in, CPU baseline, mAP delta, extra configs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's detections as "
+                    "DIR/detections.npy (ranks, classes, max_dets, 5) and DIR/counts.npy (ranks, classes), float32")
+    ap.add_argument("--no-upload", action="store_true", help="--full: skip the extra region that uploads every frame inside the step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cu-mask", default="none", choices=["none", "xcd", "rows", "xcd2"],
                     help="experiment: give every frame stream its own share of the CUs (hipExtStreamCreateWithCUMask): 'xcd' = "
@@ -528,7 +537,7 @@ def parse_args(argv=None):
     ap.add_argument("--drop-in-frames", type=int, default=240, help="frames per timed test_net call")
     ap.add_argument("--cpu-frames", type=int, default=3)
     ap.add_argument("--map-frames", type=int, default=8, help="frames (seeds 0..n-1, BASELINE configs[4]'s set) of the mAP-delta leg")
-    ap.add_argument("--layers", action="store_true", help="print the per-layer conv table to stderr")
+    ap.add_argument("--layers", action="store_true", help="--full: print the per-layer conv table to stderr")
     ap.add_argument("--rehearse-collate", action="store_true",
                     help="control-flow rehearsal WITHOUT a GPU (CPU test of the N > 1 launcher): ranks exchange synthetic "
                          "records over gloo through the same step / gather / verify / report code; measures nothing")
@@ -593,6 +602,20 @@ def masked_stream(device, k, n, mode, num_cu=256, num_xcd=8):
 def rehearsal_record(frame_id, numel):
     """Deterministic stand-in for a detection record (rehearsal mode only)."""
     return torch.arange(numel, dtype=torch.float32) * 0.5 + float(frame_id)
+
+
+def dump_outputs(out_dir, record):
+    """--dump-outputs: the collated record of one step (ranks, numel) as the arrays its caller unpacks
+    (collate.unpack_records): detections.npy (ranks, classes, MAX_DETS, 5) [x1, y1, x2, y2, score] with the rows past each
+    class's count zeroed, and counts.npy (ranks, classes), both float32."""
+    rec = record.detach().cpu().numpy().astype(np.float32).reshape(record.shape[0], -1)
+    split = NUM_CLASSES * MAX_DETS * 5
+    dets = rec[:, :split].reshape(-1, NUM_CLASSES, MAX_DETS, 5)
+    counts = rec[:, split:split + NUM_CLASSES]
+    valid = np.arange(MAX_DETS)[None, None, :] < counts[:, :, None]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "detections.npy"), np.where(valid[..., None], dets, 0.0).astype(np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), counts.astype(np.float32))
 
 
 def main(argv=None):
@@ -733,8 +756,8 @@ def main(argv=None):
     if not rehearsal and args.plans and not plans_loaded and rank == 0:
         with open(args.plans, "w") as f:
             json.dump(_ops.export_conv_plans(), f)
-    # the timed region is EXACTLY --steps steps; when that is short (the driver's 20 steps are ~0.1 s) it is repeated, every
-    # repetition fenced on both sides, until about MIN_TIMED_S of timed work exists, and the MEDIAN repetition is reported
+    # the timed region is EXACTLY --steps steps, timed once by default; --regions R repeats it R times, every repetition
+    # fenced on both sides, and reports the MEDIAN repetition (--regions 0: until about MIN_TIMED_S of timed work exists)
     n_regions = args.regions
     if n_regions <= 0:
         est = (warm_elapsed / args.warmup * args.steps) if warm_elapsed else 0.0
@@ -747,10 +770,12 @@ def main(argv=None):
     regions = [region(args.steps, source) for _ in range(n_regions)]
     order = sorted(range(n_regions), key=lambda r: regions[r][0])
     elapsed, own_elapsed, _, gathers = regions[order[n_regions // 2]]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, regions[-1][2][args.steps - 1])
     upload = None
-    if not rehearsal and not args.no_upload:
-        # same steps, every frame uploaded host -> device inside the step; median of (up to) three regions
-        ups = sorted((region(args.steps, frames_pinned) for _ in range(min(3, n_regions))), key=lambda r: r[0])
+    if args.full and not rehearsal and not args.no_upload:
+        # same steps, every frame uploaded host -> device inside the step; median of three regions
+        ups = sorted((region(args.steps, frames_pinned) for _ in range(3)), key=lambda r: r[0])
         upload = ups[len(ups) // 2]
         upload_hosts = [u[2] for u in ups]
     per_rank = [own_elapsed]
@@ -768,59 +793,61 @@ def main(argv=None):
         dist.all_gather_into_tensor(allr, own)
         per_rank = [float(v) for v in allr.cpu()]
 
-    # ---- verification of the timed records (untimed): every timed step's record must equal, bit for bit, what the
-    # eager single-stream path returns for the same frame; with N > 1 the expected records of all ranks are exchanged
-    # once more so that every rank checks every row the timed all-gathers delivered
-    if rehearsal:
-        expected = torch.stack([torch.stack([rehearsal_record(r + world * j, numel) for j in range(n_resident)])
-                                for r in range(world)])
-    else:
-        from faster_rcnn_pytorch_multimodal_amd.model.test import detect_frame_device
-        own_expected = torch.zeros((n_resident, numel), device=device)
-        for j in range(n_resident):
-            dets, counts = detect_frame_device(net, frames[j], info, THRESH, MAX_DETS, MAX_DETS)
-            collate.pack_record(dets, counts, own_expected[j])
-        torch.cuda.synchronize()
-        if use_dist:
-            expected = collate.gather_records((own_expected if backend == "nccl" else own_expected.cpu()).view(-1))
-            expected = expected.view(world, n_resident, numel).cpu()
+    verification = None
+    if args.full:
+        # ---- verification of the timed records (untimed, --full): every timed step's record must equal, bit for bit,
+        # what the eager single-stream path returns for the same frame; with N > 1 the expected records of all ranks are
+        # exchanged once more so that every rank checks every row the timed all-gathers delivered
+        if rehearsal:
+            expected = torch.stack([torch.stack([rehearsal_record(r + world * j, numel) for j in range(n_resident)])
+                                    for r in range(world)])
         else:
-            expected = own_expected.cpu().unsqueeze(0)
-    distinct = len({expected[0, j].numpy().tobytes() for j in range(n_resident)})
-    checked = [r[2] for r in regions] + (upload_hosts if upload else [])
-    bad = [(ri, i) for ri, host in enumerate(checked) for i in range(args.steps)
-           if not torch.equal(host[i], expected[:, i % n_resident, :])]
-    if use_dist:
-        flag = torch.tensor([len(bad)], dtype=torch.int64, device=gather_dev)
-        dist.all_reduce(flag, op=dist.ReduceOp.SUM)
-        n_bad = int(flag.item())
-    else:
-        n_bad = len(bad)
-    if n_bad or (distinct < 2 and n_resident > 1):
-        print("bench.py: rank %d: %d timed records differ from the eager path (first at (region, step) %s); %d distinct "
-              "expected records" % (rank, len(bad), bad[:8], distinct), file=sys.stderr)
+            from faster_rcnn_pytorch_multimodal_amd.model.test import detect_frame_device
+            own_expected = torch.zeros((n_resident, numel), device=device)
+            for j in range(n_resident):
+                dets, counts = detect_frame_device(net, frames[j], info, THRESH, MAX_DETS, MAX_DETS)
+                collate.pack_record(dets, counts, own_expected[j])
+            torch.cuda.synchronize()
+            if use_dist:
+                expected = collate.gather_records((own_expected if backend == "nccl" else own_expected.cpu()).view(-1))
+                expected = expected.view(world, n_resident, numel).cpu()
+            else:
+                expected = own_expected.cpu().unsqueeze(0)
+        distinct = len({expected[0, j].numpy().tobytes() for j in range(n_resident)})
+        checked = [r[2] for r in regions] + (upload_hosts if upload else [])
+        bad = [(ri, i) for ri, host in enumerate(checked) for i in range(args.steps)
+               if not torch.equal(host[i], expected[:, i % n_resident, :])]
         if use_dist:
-            dist.destroy_process_group()
-        raise SystemExit(3)
-    import hashlib
-    host_rec = regions[order[n_regions // 2]][2]
-    checksum = hashlib.sha1(host_rec.numpy().tobytes()).hexdigest()[:16]
-    dets_last = host_rec[args.steps - 1, 0 if not use_dist else rank]
-    verification = {"timed_steps_checked": args.steps, "regions_checked": len(checked), "equal_to_eager_path": True,
-                    "records_sha1_16": checksum,
-                    "distinct_frames_per_rank": n_resident, "distinct_expected_records": distinct,
-                    "frame_rotation": "step i replays frame i %% %d on runner i %% %d (coprime): every runner sees every frame, "
-                                      "and its output buffers are overwritten with NaN / -1 before each replay, so a replay that "
-                                      "did not execute cannot pass" % (n_resident, n_streams),
-                    "detections_per_class_last_step": [int(v) for v in dets_last[NUM_CLASSES * MAX_DETS * 5:]],
-                    "what": "every timed step's record of every timed region (collated in blocks of %d frames and copied "
-                            "device->host inside the timed region) equals the eager single-stream record of the same frame, "
-                            "bit for bit; tests/test_timed_path.py compares the same arrangement with the CPU oracle"
-                            % gather_every}
+            flag = torch.tensor([len(bad)], dtype=torch.int64, device=gather_dev)
+            dist.all_reduce(flag, op=dist.ReduceOp.SUM)
+            n_bad = int(flag.item())
+        else:
+            n_bad = len(bad)
+        if n_bad or (distinct < 2 and n_resident > 1):
+            print("bench.py: rank %d: %d timed records differ from the eager path (first at (region, step) %s); %d distinct "
+                  "expected records" % (rank, len(bad), bad[:8], distinct), file=sys.stderr)
+            if use_dist:
+                dist.destroy_process_group()
+            raise SystemExit(3)
+        import hashlib
+        host_rec = regions[order[n_regions // 2]][2]
+        checksum = hashlib.sha1(host_rec.numpy().tobytes()).hexdigest()[:16]
+        dets_last = host_rec[args.steps - 1, 0 if not use_dist else rank]
+        verification = {"timed_steps_checked": args.steps, "regions_checked": len(checked), "equal_to_eager_path": True,
+                        "records_sha1_16": checksum,
+                        "distinct_frames_per_rank": n_resident, "distinct_expected_records": distinct,
+                        "frame_rotation": "step i replays frame i %% %d on runner i %% %d (coprime): every runner sees every frame, "
+                                          "and its output buffers are overwritten with NaN / -1 before each replay, so a replay that "
+                                          "did not execute cannot pass" % (n_resident, n_streams),
+                        "detections_per_class_last_step": [int(v) for v in dets_last[NUM_CLASSES * MAX_DETS * 5:]],
+                        "what": "every timed step's record of every timed region (collated in blocks of %d frames and copied "
+                                "device->host inside the timed region) equals the eager single-stream record of the same frame, "
+                                "bit for bit; tests/test_timed_path.py compares the same arrangement with the CPU oracle"
+                                % gather_every}
 
-    # ---- the collective on its own (N > 1): HIP-event timing of the all-gather of one record on one stream
+    # ---- the collective on its own (N > 1, --full): HIP-event timing of the all-gather of one record on one stream
     allgather_us = None
-    if use_dist and not rehearsal and backend == "nccl":
+    if args.full and use_dist and not rehearsal and backend == "nccl":
         reps = 50
         blk = torch.zeros(gather_every * numel, device=device)
         out_blk = torch.zeros((world, gather_every * numel), device=device)
@@ -851,15 +878,15 @@ def main(argv=None):
                                 "frame uploaded from pinned host memory inside the step)"},
             "timed_regions": {"count": n_regions, "reported": "median", "steps_each": args.steps,
                               "ms_each": [1e3 * regions[r][0] for r in range(n_regions)],
-                              "why": "a region is EXACTLY --steps steps between two fences; it is repeated until ~%.1f s "
-                                     "of timed work exists so that a 20-step run is not a 0.1 s sample" % MIN_TIMED_S},
+                              "why": "a region is EXACTLY --steps steps between two fences; --regions R repeats it R times "
+                                     "(0: until ~%.1f s of timed work exists)" % MIN_TIMED_S},
             "verification": verification,
         }
         if upload is not None:
             out["with_host_upload"] = {"value": world * args.steps / upload[0], "unit": "frames/s",
                                        "ms_per_step": 1e3 * upload[0] / args.steps,
                                        "bytes_per_frame": int(frames_pinned[0].numel() * 4),
-                                       "what": "median of up to 3 regions of --steps steps; each step copies its frame from pinned host memory "
+                                       "what": "median of 3 regions of --steps steps; each step copies its frame from pinned host memory "
                                                "on the frame's stream (lib/model/test.py:75 hands test_frame a host blob)"}
         if use_dist:
             out["collective"] = {"backend": dist.get_backend(), "is_rccl": dist.get_backend() == "nccl",
@@ -878,7 +905,7 @@ def main(argv=None):
         if rehearsal:
             out["data"] = "rehearsal: synthetic records over gloo, no device work - NOT a measurement"
             out["value"] = None
-        else:
+        elif args.full:
             conv = conv_roofline(net, frames[0], info, steps=min(args.steps, 5))
             run_plans = _ops.export_conv_plans()
             run_sha = plans_sha(run_plans)
@@ -980,7 +1007,7 @@ def main(argv=None):
                 torch.cuda.empty_cache()
                 out["drop_in_uncertainty"] = drop_in_uncertainty(device, max(args.steps, args.drop_in_frames),
                                                                  frames_host, info)
-    if rank == 0 and world == 1 and not rehearsal and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and not rehearsal and not args.no_extra_configs:
         torch.cuda.empty_cache()
         out["extra_configs"] = extra_configs(args.steps)
     if use_dist:

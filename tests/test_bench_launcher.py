@@ -27,7 +27,8 @@ def test_gpus_2_self_launches_and_collates_over_gloo(gather_every):
     """Records are collated in blocks of `gather_every` frames (one all-gather per block, a partial last block included);
     the verification inside bench.py requires step i, row r of what arrived on the host to be rank r's record of ITS
     i-th frame - collated order = frame order of the sharded loop - for both block sizes."""
-    res = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--rehearse-collate", "--gather-every", str(gather_every)])
+    res = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--rehearse-collate", "--gather-every", str(gather_every),
+                "--full"])
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout                      # rank 0 only
@@ -53,7 +54,7 @@ def test_gpus_8_rehearsal_frame_sharding_blocks_and_device_binding():
     """The 8-rank run of BASELINE.json configs[4] rehearsed over gloo (the driver's `--gpus 8` can then only fail on RCCL
     itself): frame seed r + 8 j on rank r (seeds 0..7 in the first step), ONE all-gather per block of 8 frames, every rank
     bound to cuda:LOCAL_RANK, the audit fields of the `collective` object, all records verified in collated order."""
-    res = _run(["--gpus", "8", "--steps", "16", "--warmup", "2", "--rehearse-collate"], timeout=600)
+    res = _run(["--gpus", "8", "--steps", "16", "--warmup", "2", "--rehearse-collate", "--full"], timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout
@@ -68,6 +69,30 @@ def test_gpus_8_rehearsal_frame_sharding_blocks_and_device_binding():
     assert col["record_bytes_per_rank"] * 8 == col["block_bytes_per_rank"]
     ver = out["verification"]
     assert ver["equal_to_eager_path"] is True and ver["timed_steps_checked"] == 16 and ver["regions_checked"] >= 1
+
+
+def test_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full the run times ONE region of exactly --steps steps, skips the verification leg, and --dump-outputs
+    writes the last timed step's collated record (one row per rank) as float32 arrays."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    res = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--rehearse-collate", "--dump-outputs", str(tmp_path / "out")])
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 5 and out["timed_regions"]["count"] == 1 and out["timed_regions"]["steps_each"] == 5
+    assert len(out["timed_regions"]["ms_each"]) == 1 and out["verification"] is None and "ms_per_step" in out
+    dets = np.load(tmp_path / "out" / "detections.npy")
+    counts = np.load(tmp_path / "out" / "counts.npy")
+    assert dets.dtype == counts.dtype == np.float32
+    assert dets.shape == (2, bench.NUM_CLASSES, bench.MAX_DETS, 5) and counts.shape == (2, bench.NUM_CLASSES)
+    split = bench.NUM_CLASSES * bench.MAX_DETS * 5
+    for r in range(2):                                          # step 4 replays frame 4 % 5 (--streams 4: 5 resident frames)
+        rec = bench.rehearsal_record(r + 2 * 4, split + bench.NUM_CLASSES).numpy()
+        assert np.array_equal(counts[r], rec[split:])
+        assert np.array_equal(dets[r].reshape(-1), rec[:split])   # rehearsal counts exceed MAX_DETS: every row kept
 
 
 def test_device_binding_rule():

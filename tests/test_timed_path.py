@@ -225,7 +225,8 @@ def test_bench_runs_its_collective_path_over_rccl_with_one_rank(hip):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR"):
         env.pop(k, None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "4", "--no-cpu-baseline"],
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "4", "--full",
+                          "--no-cpu-baseline"],
                          env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])

@@ -13,9 +13,9 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
 rm -f $O/${TAG}_plans.json
-python3 $R/bench.py --retune --plans $O/${TAG}_plans.json > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 $R/bench.py --full --retune --plans $O/${TAG}_plans.json > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 echo "bench done"; cut -c1-300 $O/${TAG}_bench.json
-QUIET="--no-cpu-baseline --no-drop-in --no-extra-configs"
+QUIET="--full --no-cpu-baseline --no-drop-in --no-extra-configs"   # --full: the isolated conv roofline frames
 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof -o ${TAG} -- python3 $R/bench.py --plans $O/${TAG}_plans.json --steps 30 --warmup 5 $QUIET > $O/${TAG}_prof.log 2>&1
 echo "kernel trace done"
 for C in FETCH_SIZE WRITE_SIZE MfmaUtil; do

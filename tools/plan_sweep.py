@@ -63,7 +63,7 @@ def variants(base):
 
 def run_bench(plans_path, steps, streams):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--plans", plans_path, "--steps", str(steps), "--warmup", "8",
-           "--no-cpu-baseline", "--streams", str(streams)]
+           "--full", "--no-cpu-baseline", "--streams", str(streams)]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT)
     for line in res.stdout.splitlines():
         if line.startswith("{"):
