@@ -1647,7 +1647,7 @@ extern "C" int frcnn_conv2d_export_plans(int* out, int capacity_entries) {
 
 extern "C" int frcnn_conv2d_import_plans(const int* in, int entries) {
   FRCNN_REQUIRE(in && entries >= 0, "conv2d_import_plans: null table");
-  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  // every entry is checked before any is inserted: a refused table leaves the cache as it was
   for (int e = 0; e < entries; ++e) {
     const int* row = in + e * 13;
     const int code = row[10] >> 4, cfg = row[10] & 15;
@@ -1655,6 +1655,23 @@ extern "C" int frcnn_conv2d_import_plans(const int* in, int entries) {
     FRCNN_REQUIRE(row[10] >= 0 && cfg < kNumTiles && code <= 2 && (!fuse_in || (cfg == 5 && row[3] % BK == 0)) && row[11] >= 1 && row[11] <= 64 && row[12] >= 1 &&
                       (algo == 0 || (row[11] == 1 && winograd_ok(row[5], row[6], row[7], row[8], row[3], row[4], row[9]))),   // a residual key (row[9] >= 256) fails winograd_ok: no Winograd plan for it
                   "conv2d_import_plans: entry %d is not a valid plan (tile %d, splits %d)", e, row[10], row[11]);
+    if (algo == 1) continue;   // the Winograd GEMM derives its own K-steps (launch_winograd)
+    // the implicit-GEMM kernels run K-steps [z * steps_per_split, min((z + 1) * steps_per_split, ksteps)) in split z: the
+    // splits must cover every K-step and none may be empty - the relation choose_plan and tune_candidates obey
+    const long ktot = (long)row[5] * row[6] * row[3];
+    FRCNN_REQUIRE(row[3] >= 1 && row[5] >= 1 && row[6] >= 1 && ktot <= INT32_MAX,
+                  "conv2d_import_plans: entry %d is not a valid plan (filter %dx%d over %d channels)", e, row[5], row[6], row[3]);
+    const long ksteps = (ktot + BK - 1) / BK;
+    FRCNN_REQUIRE((ksteps + row[12] - 1) / row[12] == row[11],
+                  "conv2d_import_plans: entry %d is not a valid plan (%d splits x %d steps per split for %ld K-steps: "
+                  "needs ceil(K-steps / steps per split) == splits, else K-steps are dropped or a split is empty)",
+                  e, row[11], row[12], ksteps);
+  }
+  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  for (int e = 0; e < entries; ++e) {
+    const int* row = in + e * 13;
+    const int code = row[10] >> 4, cfg = row[10] & 15;
+    const int algo = code >= 1 ? 1 : 0, fuse_in = code == 2 ? 1 : 0;
     ShapeKey key;
     for (int i = 0; i < 10; ++i) key[i] = row[i];
     Plan pl{cfg, row[11], row[12]};

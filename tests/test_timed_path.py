@@ -4,6 +4,9 @@ tolerance written below), at the full 1000x600 size of BASELINE.json configs[1].
 
 Reference loop: lib/model/test.py:183-228 (frame_detect -> filter_and_draw_prep -> max_dets cut per class).
 """
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -13,6 +16,7 @@ from oracle import frcnn_oracle as O
 
 pytestmark = pytest.mark.gpu
 
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 DEV = "cuda:0"
 N_STREAMS = 4
 INFO = np.array([0, bench.W, 0, bench.H, 0, 0, 1.0], np.float32)
@@ -102,17 +106,21 @@ def _pred_boxes_fp64(sd, frame_host, rois_r):
     return pb, cls_prob
 
 
-@pytest.mark.parametrize("conv_algo", [0, 1, 2])
+@pytest.mark.parametrize("conv_algo", [0, 1, 2, "table"])
 def test_timed_path_against_cpu_oracle_structured_rpn(hip, conv_algo):
     """Graph x 4 streams vs O.frame_detect on the structured-RPN variant of the frames (injected RPN
     logits / deltas make the ranking of the 59 850 anchors well-conditioned; backbone, RoIAlign, layer4, heads and the
     per-class filter are each path's own).  Proposal indices bit-exact, detection records within the tolerance.
-    conv_algo (frcnn_conv2d_set_algo): 0 = whatever the autotuner picks (the bench's mode), 1 = implicit GEMM only,
-    2 = Winograd F(2x2,3x3) on every eligible 3x3 layer - the same bounds hold for each."""
+    conv_algo (frcnn_conv2d_set_algo): 0 = whatever the autotuner picks on this box, 1 = implicit GEMM only,
+    2 = Winograd F(2x2,3x3) on every eligible 3x3 layer; "table" = mode 0 with the committed plan table
+    profiles/<bench.PLANS_FILE> installed, which is what bench.py times by default - the same bounds hold for each."""
     from faster_rcnn_pytorch_multimodal_amd import ops as _ops_mod
     hip.frcnn_conv2d_clear_plans()
-    _ops_mod.set_conv_algo(conv_algo)
+    _ops_mod.set_conv_algo(0 if conv_algo == "table" else conv_algo)
     try:
+        if conv_algo == "table":
+            with open(os.path.join(ROOT, "profiles", bench.PLANS_FILE)) as f:
+                _ops_mod.import_conv_plans(json.load(f))
         _timed_path_against_cpu_oracle()
     finally:
         _ops_mod.set_conv_algo(0)
