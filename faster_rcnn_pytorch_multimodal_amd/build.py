@@ -30,6 +30,7 @@ SOURCES = {
     "prep.hip": ["-ffp-contract=off"],
     "batchnorm.hip": ["-ffp-contract=off"],
     "voxelize.hip": ["-ffp-contract=off"],
+    "lidar_augment.hip": ["-ffp-contract=off"],
 }
 COMMON_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -70,6 +70,8 @@ def _defaults():
     c.TEST = dict(SCALES=(1.0,), NMS_THRESH=0.6, BBOX_REG=True, HAS_RPN=True, RPN_NMS_THRESH=0.7,
                   RPN_PRE_NMS_TOP_N=6000, RPN_POST_NMS_TOP_N=300, MODE='nms', RPN_TOP_N=5000, IGNORE_DC=False,
                   ITER=1, AUGMENT_EN=False, TOD_FILTER_LIST=['Day', 'Night', 'Dawn/Dusk'],
+                  # LiDAR rain simulation / point dropout at test time (config.py:450-453; minibatch.py:397-425)
+                  RAIN_SIM_EN=False, DROPOUT_EN=False, RAIN_RATE=1,      # mm/h
                   # not in the reference: how test_net / test_frame / run_eval execute a frame (model/frame_graph.FramePool)
                   FRAME_GRAPHS=True,       # replay each frame as a captured hipGraph (False: eager launches)
                   FRAMES_IN_FLIGHT=4,      # test_net: frames in flight, one HIP stream each
@@ -91,8 +93,15 @@ def _defaults():
                    NUM_SLICES=12, NUM_META_CHANNEL=3, NUM_CHANNEL=15, MAX_PTS_PER_VOXEL=32, MAX_NUM_VOXEL=25000,
                    ANCHORS=np.array([[4.73, 2.08, 1.77]]), ANCHOR_SCALES=np.array([[1]]),
                    ANCHOR_ANGLES=np.array([0, np.pi / 2]), NUM_BBOX_ELEM=7,
-                   REG_LOSS_WEIGHT=[1.0] * 7, EN_RY_SIN=True)
+                   REG_LOSS_WEIGHT=[1.0] * 7, EN_RY_SIN=True,
+                   # training augmentations of the point cloud (config.py:407-413; roi_data_layer/lidar_augment.py)
+                   SHUFFLE_PC=False, EN_AUG_FLIPS=True, EN_AUG_GAUSS_DISTORT=True, EN_AUG_DROPOUT=True,
+                   EN_AUG_ROTATE=False, EN_AUG_SWAP_X_Y=True)
     c.IMAGE = dict(NUM_BBOX_ELEM=4)
+    # sensor range in metres, read by the rain simulation as cfg[cfg.DB_NAME.upper()].LIDAR_MAX_RANGE (config.py:431-449)
+    c.WAYMO = dict(LIDAR_MAX_RANGE=200)
+    c.KITTI = dict(LIDAR_MAX_RANGE=120)
+    c.CADC = dict(LIDAR_MAX_RANGE=200)
     return c
 
 

@@ -801,6 +801,51 @@ def bev_voxelize(points, pc_range, voxel_size, z_shift, max_points, max_voxels, 
     return bev, count
 
 
+# frcnn_lidar_augment: flag bits and parameter slots of include/frcnn_hip.h
+AUG_GAUSS, AUG_DROPOUT, AUG_ROTATE, AUG_SWAP_XY, AUG_FLIP_Y, AUG_FLIP_X, AUG_RAIN, AUG_TEST_DROPOUT = (1 << b for b in range(8))
+# counter-based draws of the kernel (csrc/rng.h): normal01 streams of the distortion (x, y, z) and of the rain shift,
+# uniform01 streams of the two keep masks
+AUG_STREAM = {'gauss_x': 32, 'gauss_y': 33, 'gauss_z': 34, 'rain': 35, 'dropout': 72, 'test_dropout': 73}
+
+
+def lidar_augment_points(points, params, seed, pc_extents, seed_dev=None, out=None, max_blocks=0):
+    """Per-point LiDAR augmentation / rain simulation in front of ``bev_voxelize`` (frcnn_lidar_augment;
+    lib/roi_data_layer/minibatch.py:274-428).  ``points`` (N, F>=4) device tensor; ``params``: the decision record
+    (``roi_data_layer.lidar_augment.LidarAugment`` or any object with its fields: flip_x, flip_y, gauss (sx, sy, sz) or
+    None, p_keep or None, rotation (radians) or None, swap_xy, rain_rate or None, rain_max_range, test_dropout);
+    ``pc_extents`` = [X0, Y0, Z0, X1, Y1, Z1].  Returns (points_out, kept_count): dropped rows carry NaN in x, y, z,
+    kept_count is a one-element int32 device tensor (surviving points inside the extents).  ``out=points`` works in place."""
+    import math
+    lib = _hip.load()
+    _dev_f32(points, "points")
+    if points.dim() != 2 or points.shape[1] < 4 or points.shape[0] == 0:
+        raise _hip.HipError("lidar_augment_points: points must be (N>0, F>=4), got %s" % (tuple(points.shape),))
+    if out is None:
+        out = torch.empty_like(points)
+    elif _dev_f32(out, "out").shape != points.shape:
+        raise _hip.HipError("lidar_augment_points: out %s != points %s" % (tuple(out.shape), tuple(points.shape)))
+    flags, vals = 0, [0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0]
+    if params.gauss is not None:
+        flags |= AUG_GAUSS
+        vals[0:3] = [float(v) for v in params.gauss]
+    if params.p_keep is not None:
+        flags |= AUG_DROPOUT
+        vals[3] = float(params.p_keep)
+    if params.rotation is not None:
+        flags |= AUG_ROTATE
+        vals[4], vals[5] = math.cos(float(params.rotation)), math.sin(float(params.rotation))
+    if params.rain_rate is not None:
+        flags |= AUG_RAIN
+        vals[6], vals[7] = float(params.rain_rate), float(params.rain_max_range)
+    flags |= (AUG_SWAP_XY if params.swap_xy else 0) | (AUG_FLIP_Y if params.flip_y else 0)
+    flags |= (AUG_FLIP_X if params.flip_x else 0) | (AUG_TEST_DROPOUT if params.test_dropout else 0)
+    kept = torch.empty((1,), dtype=torch.int32, device=points.device)
+    _hip.check(lib.frcnn_lidar_augment(_ptr(points), points.shape[0], points.shape[1], _hip.float_array(pc_extents), flags,
+                                       _hip.float_array(vals), int(seed) & 0xFFFFFFFF, _seed_dev(seed_dev), _ptr(out),
+                                       _ptr(kept), int(max_blocks), _stream()), "frcnn_lidar_augment")
+    return out, kept
+
+
 # ----------------------------------------------------------------------------------------------
 # training path
 # ----------------------------------------------------------------------------------------------

@@ -1,14 +1,18 @@
 """LiDAR input producer - counterpart of ``_get_lidar_blob`` (lib/roi_data_layer/minibatch.py:237-516) for ONE frame
 whose points are already in memory: range filter (:232-235), voxelisation and the BEV scatter (:434-512) run as
-``frcnn_bev_voxelize`` on the device; file parsing, FOV calibration and the augmentations (:250-431) stay with the
-caller (dataset plumbing, out of scope).  Returns the same ``(infos, blob)`` the reference's data layer hands to
+``frcnn_bev_voxelize`` on the device, the per-point augmentations and the test-time rain simulation in front of them
+(:274-428) as ``frcnn_lidar_augment``; file parsing and FOV calibration (:250-273) stay with the caller (dataset
+plumbing, out of scope).  Returns the same ``(infos, blob)`` the reference's data layer hands to
 ``Network.forward``: blob (1, num_y_voxel, num_x_voxel, cfg.LIDAR.NUM_CHANNEL) NHWC on the device,
 info = [0, num_x_voxel, 0, num_y_voxel, 0, NUM_SLICES, scale].
 
 The reference-named entry points (``_get_image_blob``, ``_get_lidar_blob``, ``get_minibatch``: what
 ``lib/model/test.py:32-44`` and ``lib/roi_data_layer/layer.py:66-82`` call) load ONE frame from a file and hand it to the
-device producers (``frcnn_prep_image``, ``frcnn_bev_voxelize``).  Augmentation (imgaug, flips, rain simulation:
-minibatch.py:250-431,542-664) is dataset tooling outside the accelerated path: ``augment_en=True`` raises.
+device producers (``frcnn_prep_image``, ``frcnn_lidar_augment``, ``frcnn_bev_voxelize``).  LiDAR frames: ``augment_en=True``
+draws the reference's flips / distortion / dropout / rotation / swap per frame (``roi_data_layer/lidar_augment.py``),
+moves the points on the device and the gt boxes on the host; ``mode='test'`` applies cfg.TEST.RAIN_SIM_EN / DROPOUT_EN.
+Image augmentation (imgaug: minibatch.py:542-664) is dataset tooling outside the accelerated path: ``augment_en=True``
+raises for images.
 """
 import numpy as np
 import torch
@@ -80,7 +84,7 @@ def read_point_cloud_file(filename):
 
 def _no_augmentation(augment_en):
     if augment_en:
-        raise NotImplementedError("augment_en=True: the imgaug / flip / rain augmentations of lib/roi_data_layer/minibatch.py "
+        raise NotImplementedError("augment_en=True: the imgaug augmentations of lib/roi_data_layer/minibatch.py:542-664 "
                                   "are dataset tooling outside this package; pass augment_en=False")
 
 
@@ -103,14 +107,21 @@ def _get_image_blob(roidb, im_scale, augment_en=False, mode='train', device='cud
 
 
 def _get_lidar_blob(roidb, pc_extents, scale, augment_en=False, mode='train', device='cuda'):
-    """minibatch.py:237-516 without the augmentations: file -> points -> ``get_lidar_blob`` (range filter, voxel
-    generator and BEV scatter on the device).  ``pc_extents`` is what the reference passes (cfg.LIDAR.*_RANGE); the
-    voxeliser reads the same ranges from cfg.  Waymo scans carry the elongation in column 4 (:496-499)."""
+    """minibatch.py:237-516: file -> points -> augmentation / rain simulation (``frcnn_lidar_augment``, only when a step
+    is switched on) -> ``get_lidar_blob`` (range filter, voxel generator and BEV scatter on the device).  ``pc_extents`` is
+    what the reference passes (cfg.LIDAR.*_RANGE); the voxeliser reads the same ranges from cfg.  Waymo scans carry the
+    elongation in column 4 (:496-499).  Returns (infos, None, local_roidb) when no point is left (:428-432)."""
     from copy import deepcopy
-    _no_augmentation(augment_en)
+    from .lidar_augment import augment_gt_boxes, draw_lidar_augmentation
     if len(roidb) != 1:
         raise NotImplementedError("single-frame batches only (minibatch.py:111)")
+    if cfg.LIDAR.SHUFFLE_PC:
+        raise NotImplementedError("cfg.LIDAR.SHUFFLE_PC: the reference's line (minibatch.py:292-293) replaces the cloud by "
+                                  "None and cannot run; keep it False")
     if mode == 'test':
+        if augment_en:
+            raise NotImplementedError("augment_en=True with mode='test': the reference flags a roidb entry there "
+                                      "(minibatch.py:295) and a test frame has none; pass augment_en=False")
         filen, local_roidb = roidb[0], None
     else:
         filen, local_roidb = roidb[0]['filename'], deepcopy(roidb)
@@ -121,6 +132,19 @@ def _get_lidar_blob(roidb, pc_extents, scale, augment_en=False, mode='train', de
         raise ValueError("pc_extents %s differ from cfg.LIDAR.*_RANGE %s" % (list(pc_extents), expected))
     points = read_point_cloud_file(filen)
     elongation = 4 if (cfg.DB_NAME == 'waymo' and points.shape[1] > 4) else None
+    if augment_en or (mode == 'test' and (cfg.TEST.RAIN_SIM_EN or cfg.TEST.DROPOUT_EN)):
+        aug = draw_lidar_augmentation(augment_en=augment_en, mode=mode)
+        if not aug.identity:
+            if points.shape[0] == 0:
+                return [], None, local_roidb
+            points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(device, non_blocking=True)
+            points, kept = ops.lidar_augment_points(points, aug, aug.seed, expected, out=points)
+            if local_roidb is not None:
+                augment_gt_boxes(local_roidb[0], aug)
+            if int(kept.item()) <= 0:                                                # :428-432
+                print('No PC points in frame {} FLIP_X: {} FLIP_Y: {} ROT: {} SWAP_X_Y: {}'.format(
+                    filen, aug.flip_x, aug.flip_y, aug.rotation is not None, aug.swap_xy))
+                return [], None, local_roidb
     infos, blob = get_lidar_blob(points, scale, device=device, elongation=elongation)
     return [np.asarray(infos[0], dtype=np.float32)], blob, local_roidb
 
@@ -151,6 +175,8 @@ def get_lidar_minibatch(roidb, num_classes, augment_en, scale, cnt):
     extents = [cfg.LIDAR.X_RANGE[0], cfg.LIDAR.Y_RANGE[0], cfg.LIDAR.Z_RANGE[0],
                cfg.LIDAR.X_RANGE[1], cfg.LIDAR.Y_RANGE[1], cfg.LIDAR.Z_RANGE[1]]
     infos, pc_blob, local_roidb = _get_lidar_blob(roidb, extents, scale, augment_en)
+    if pc_blob is None:                                                              # :139-140: go to the next frame
+        return None
     info, entry = infos[0], local_roidb[0]
     gt_inds = np.where(np.asarray(entry['ignore']) == 0)[0]
     width = cfg.LIDAR.NUM_BBOX_ELEM + 1
@@ -159,7 +185,7 @@ def get_lidar_minibatch(roidb, num_classes, augment_en, scale, cnt):
     gt_boxes[:, 0:2] *= scale
     gt_boxes[:, 3:5] *= scale
     gt_boxes[:, -1] = np.asarray(entry['gt_classes'])[gt_inds]
-    blobs = {'data': pc_blob, 'flipped': False, 'filename': entry['filename'], 'gt_boxes': gt_boxes,
+    blobs = {'data': pc_blob, 'flipped': entry['flipped'], 'filename': entry['filename'], 'gt_boxes': gt_boxes,
              'gt_boxes_dc': np.empty(0) * scale, 'info': np.array(info, dtype=np.float32)}
     return blobs if len(gt_boxes) else None
 

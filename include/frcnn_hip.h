@@ -400,6 +400,41 @@ int frcnn_bev_voxelize(const float* points, int num_points, int point_stride, co
                        int num_meta, int elongation_col, float* bev, int* num_voxels, void* ws, size_t ws_bytes,
                        void* stream);
 
+/* LiDAR point-cloud augmentation and test-time rain simulation (lib/roi_data_layer/minibatch.py:274-428), the per-point
+ * transforms in front of frcnn_bev_voxelize, one pass in the reference's order: filter_points on the raw point
+ * (:232-235,274), Gaussian distortion (:309-319), dropout (:321-325), rotation about z (:330-349,695-714), x/y swap
+ * (:351-373), flip y (:375-384), flip x (:386-395), rain (:397-421), test dropout with p_keep 0.8 (:422-425); `flags`
+ * selects the steps.  points / out (num_points, point_stride >= 4) rows [x,y,z,intensity,...]; out may be points itself.
+ * range_host[6] = [X0,Y0,Z0,X1,Y1,Z1] = cfg.LIDAR.*_RANGE (unshifted).  params_host[FRCNN_AUG_NUM_PARAMS]: indices
+ * FRCNN_AUG_P_* (p_keep in (0, 1] always; cos / sin of the angle computed in double and rounded once; rain rate in mm/h
+ * and cfg.<DB>.LIDAR_MAX_RANGE in m, read only with FRCNN_AUG_RAIN).  Draws are counter-based, value = f(seed + *seed_dev,
+ * stream, row index) (csrc/rng.h; seed_dev device uint32 or NULL): normal01 streams 32, 33, 34 = distortion of x, y, z,
+ * 35 = rain shift; uniform01 stream 72 = dropout, 73 = test dropout.  A dropped point keeps its row with x, y, z = NaN
+ * (frcnn_bev_voxelize's range test rejects it; row order, hence voxel numbering, is the reference's).  kept_count
+ * (device int, written by the call) = surviving points inside range_host, the reference's "no points left" test
+ * (:426-432).  max_blocks: 0 = automatic grid, > 0 caps the workgroups (test hook: the result does not depend on it). */
+#define FRCNN_AUG_GAUSS 1u
+#define FRCNN_AUG_DROPOUT 2u
+#define FRCNN_AUG_ROTATE 4u
+#define FRCNN_AUG_SWAP_XY 8u
+#define FRCNN_AUG_FLIP_Y 16u
+#define FRCNN_AUG_FLIP_X 32u
+#define FRCNN_AUG_RAIN 64u
+#define FRCNN_AUG_TEST_DROPOUT 128u
+#define FRCNN_AUG_ALL 255u
+#define FRCNN_AUG_P_SIGMA_X 0
+#define FRCNN_AUG_P_SIGMA_Y 1
+#define FRCNN_AUG_P_SIGMA_Z 2
+#define FRCNN_AUG_P_KEEP 3
+#define FRCNN_AUG_P_COS 4
+#define FRCNN_AUG_P_SIN 5
+#define FRCNN_AUG_P_RAIN_RATE 6
+#define FRCNN_AUG_P_RAIN_MAX_RANGE 7
+#define FRCNN_AUG_NUM_PARAMS 8
+int frcnn_lidar_augment(const float* points, int num_points, int point_stride, const float* range_host, unsigned flags,
+                        const float* params_host, uint32_t seed, const uint32_t* seed_dev, float* out, int* kept_count,
+                        int max_blocks, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training path (BASELINE config 4: FPN forward + backward of one train_step, lib/model/train_val.py:458)
  * ------------------------------------------------------------------------------------------- */
