@@ -31,6 +31,7 @@ SOURCES = {
     "batchnorm.hip": ["-ffp-contract=off"],
     "voxelize.hip": ["-ffp-contract=off"],
     "lidar_augment.hip": ["-ffp-contract=off"],
+    "image_augment.hip": ["-ffp-contract=off"],
 }
 COMMON_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -97,7 +97,12 @@ def _defaults():
                    # training augmentations of the point cloud (config.py:407-413; roi_data_layer/lidar_augment.py)
                    SHUFFLE_PC=False, EN_AUG_FLIPS=True, EN_AUG_GAUSS_DISTORT=True, EN_AUG_DROPOUT=True,
                    EN_AUG_ROTATE=False, EN_AUG_SWAP_X_Y=True)
-    c.IMAGE = dict(NUM_BBOX_ELEM=4)
+    c.IMAGE = dict(NUM_BBOX_ELEM=4,
+                   # not in the reference: training augmentation of the camera frame on the device (minibatch.py:540-647;
+                   # roi_data_layer/image_augment.py).  EN_AUG is the master switch: while it is False, augment_en=True
+                   # raises for image frames as before; the per-step switches follow cfg.LIDAR.EN_AUG_*
+                   EN_AUG=False, EN_AUG_FLIP=True, EN_AUG_FILTER=True, EN_AUG_NOISE=True, EN_AUG_HUE_SAT=True,
+                   EN_AUG_AFFINE=True, EN_AUG_DROPOUT=True)
     # sensor range in metres, read by the rain simulation as cfg[cfg.DB_NAME.upper()].LIDAR_MAX_RANGE (config.py:431-449)
     c.WAYMO = dict(LIDAR_MAX_RANGE=200)
     c.KITTI = dict(LIDAR_MAX_RANGE=120)

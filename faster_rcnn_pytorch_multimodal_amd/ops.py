@@ -805,7 +805,9 @@ def bev_voxelize(points, pc_range, voxel_size, z_shift, max_points, max_voxels, 
 AUG_GAUSS, AUG_DROPOUT, AUG_ROTATE, AUG_SWAP_XY, AUG_FLIP_Y, AUG_FLIP_X, AUG_RAIN, AUG_TEST_DROPOUT = (1 << b for b in range(8))
 # counter-based draws of the kernel (csrc/rng.h): normal01 streams of the distortion (x, y, z) and of the rain shift,
 # uniform01 streams of the two keep masks
-AUG_STREAM = {'gauss_x': 32, 'gauss_y': 33, 'gauss_z': 34, 'rain': 35, 'dropout': 72, 'test_dropout': 73}
+# frcnn_image_augment: normal01 streams of the additive noise (one per channel), uniform01 stream of the pixel dropout
+AUG_STREAM = {'gauss_x': 32, 'gauss_y': 33, 'gauss_z': 34, 'rain': 35, 'dropout': 72, 'test_dropout': 73,
+              'image_noise_0': 40, 'image_noise_1': 41, 'image_noise_2': 42, 'image_dropout': 86}
 
 
 def lidar_augment_points(points, params, seed, pc_extents, seed_dev=None, out=None, max_blocks=0):
@@ -844,6 +846,88 @@ def lidar_augment_points(points, params, seed, pc_extents, seed_dev=None, out=No
                                        _hip.float_array(vals), int(seed) & 0xFFFFFFFF, _seed_dev(seed_dev), _ptr(out),
                                        _ptr(kept), int(max_blocks), _stream()), "frcnn_lidar_augment")
     return out, kept
+
+
+# frcnn_image_augment: stage codes and the parameter slots per stage of include/frcnn_hip.h
+(IMG_COPY, IMG_GAUSS, IMG_AVERAGE, IMG_MEDIAN, IMG_SHARPEN, IMG_NOISE, IMG_HUE_SAT, IMG_AFFINE, IMG_DROPOUT) = range(9)
+IMG_MAX_STAGES, IMG_NUM_PARAMS = 8, 12
+
+
+def image_augment_stages(aug, height, width):
+    """``(flip, [(code, [parameters]), ...])`` of an ``ImageAugment`` record (or any object with its fields) for a frame
+    of ``height`` x ``width``: the host-side numbers of every stage, computed in double and rounded once to float32 by
+    the call (Gaussian taps, sharpen weights, the hue offset on the 0..180 circle, the inverse affine matrix).  Stages
+    that change nothing (empty filter group, 1x1 average / median) are left out."""
+    import numpy as np
+    from .roi_data_layer.image_augment import gaussian_taps, hue_offset
+    stages = []
+    for st in aug.stages:
+        kind = st[0]
+        if kind == 'gaussian':
+            taps = gaussian_taps(st[1])
+            stages.append((IMG_GAUSS, [len(taps)] + [float(t) for t in taps]))
+        elif kind == 'average':
+            if int(st[1]) != 1:
+                stages.append((IMG_AVERAGE, [int(st[1])]))
+        elif kind == 'median':
+            if int(st[1]) != 1:
+                stages.append((IMG_MEDIAN, []))
+        elif kind == 'sharpen':
+            alpha, light = float(st[1]), float(st[2])
+            stages.append((IMG_SHARPEN, [(1.0 - alpha) + alpha * (8.0 + light), -alpha]))
+        elif kind == 'noise':
+            stages.append((IMG_NOISE, [float(st[1])]))
+        elif kind == 'hue_sat':
+            stages.append((IMG_HUE_SAT, [float(hue_offset(st[1])), float(st[2])]))
+        elif kind != 'none':
+            raise _hip.HipError("image_augment: unknown stage %r" % (st,))
+    if aug.affine is not None:
+        inv = np.linalg.inv(aug.affine.matrix(width, height))
+        stages.append((IMG_AFFINE, [inv[0, 0], inv[0, 1], inv[0, 2], inv[1, 0], inv[1, 1], inv[1, 2],
+                                    float(aug.affine.order), float(aug.affine.cval)]))
+    if aug.dropout is not None:
+        stages.append((IMG_DROPOUT, [float(aug.dropout[0]), 1.0 if aug.dropout[1] else 0.0]))
+    return bool(aug.flip), stages
+
+
+def image_augment(img, aug, out=None, scratch=None, seed_dev=None, debug_pre=None):
+    """Image augmentation in front of ``prep_im_for_blob`` (frcnn_image_augment; lib/roi_data_layer/minibatch.py:540-647).
+    ``img``: uint8 (H, W, 3) device tensor in cv2.imread order; ``aug``: the decision record
+    (``roi_data_layer.image_augment.ImageAugment``).  Returns the augmented uint8 frame (``out`` or a new tensor).
+    ``scratch``: a uint8 device tensor of at least ``frcnn_image_augment_ws_bytes`` bytes (allocated when a second stage
+    needs it and none is given).  ``img``, ``out`` and ``scratch`` must be three different buffers.  ``debug_pre``: float32
+    (H, W, 3) device tensor receiving the values before rounding of a single noise / hue-saturation stage (tests)."""
+    lib = _hip.load()
+    if not isinstance(img, torch.Tensor) or not img.is_cuda:
+        raise _hip.HipError("image_augment: img must be a tensor on the MI355X (got %s); this package has no CPU path"
+                            % (getattr(img, "device", type(img)),))
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
+        raise _hip.HipError("image_augment: img must be a contiguous uint8 (H, W, 3) frame, got %s %s"
+                            % (img.dtype, tuple(img.shape)))
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if out is None:
+        out = torch.empty_like(img)
+    elif out.dtype != torch.uint8 or out.shape != img.shape or not out.is_cuda or not out.is_contiguous():
+        raise _hip.HipError("image_augment: out must be a contiguous uint8 device tensor of shape %s" % (tuple(img.shape),))
+    flip, stages = image_augment_stages(aug, h, w)
+    if len(stages) > IMG_MAX_STAGES:
+        raise _hip.HipError("image_augment: %d stages, at most %d" % (len(stages), IMG_MAX_STAGES))
+    nbytes = lib.frcnn_image_augment_ws_bytes(h, w)
+    if scratch is None and len(stages) > 1:
+        scratch = _workspace(nbytes, img.device)
+    if scratch is not None and (scratch.dtype != torch.uint8 or not scratch.is_cuda or not scratch.is_contiguous()):
+        raise _hip.HipError("image_augment: scratch must be a contiguous uint8 device tensor")
+    if debug_pre is not None and (_dev_f32(debug_pre, "debug_pre").numel() != img.numel()):
+        raise _hip.HipError("image_augment: debug_pre must hold H*W*3 floats")
+    codes = (ctypes.c_int * max(len(stages), 1))(*[c for c, _ in stages])
+    flat = []
+    for _, vals in stages:
+        flat += [float(v) for v in vals] + [0.0] * (IMG_NUM_PARAMS - len(vals))
+    _hip.check(lib.frcnn_image_augment(_ptr(img), h, w, int(flip), len(stages), codes, _hip.float_array(flat or [0.0]),
+                                       int(aug.seed) & 0xFFFFFFFF, _seed_dev(seed_dev), _ptr(scratch),
+                                       0 if scratch is None else scratch.numel(), _ptr(out), _ptr(debug_pre), _stream()),
+               "frcnn_image_augment")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -11,8 +11,11 @@ The reference-named entry points (``_get_image_blob``, ``_get_lidar_blob``, ``ge
 device producers (``frcnn_prep_image``, ``frcnn_lidar_augment``, ``frcnn_bev_voxelize``).  LiDAR frames: ``augment_en=True``
 draws the reference's flips / distortion / dropout / rotation / swap per frame (``roi_data_layer/lidar_augment.py``),
 moves the points on the device and the gt boxes on the host; ``mode='test'`` applies cfg.TEST.RAIN_SIM_EN / DROPOUT_EN.
-Image augmentation (imgaug: minibatch.py:542-664) is dataset tooling outside the accelerated path: ``augment_en=True``
-raises for images.
+Image frames: with ``cfg.IMAGE.EN_AUG`` on, ``augment_en=True`` draws the reference's flip / blur-sharpen / noise /
+hue-saturation / affine / dropout per frame (``roi_data_layer/image_augment.py``, minibatch.py:540-647), runs the pixels
+through ``frcnn_image_augment`` on the device in front of ``frcnn_prep_image`` and moves, clips and flags the gt boxes on
+the host.  The switch defaults to off: ``augment_en=True`` then raises for images, as does the test-time ``Spatter``
+corruption (:648-664) always.
 """
 import numpy as np
 import torch
@@ -82,18 +85,24 @@ def read_point_cloud_file(filename):
     raise ValueError('Cannot handle this type of binary file: %s' % filename)
 
 
-def _no_augmentation(augment_en):
-    if augment_en:
-        raise NotImplementedError("augment_en=True: the imgaug augmentations of lib/roi_data_layer/minibatch.py:542-664 "
-                                  "are dataset tooling outside this package; pass augment_en=False")
+def _no_augmentation(augment_en, mode='train'):
+    if augment_en and mode == 'test':
+        raise NotImplementedError("augment_en=True with mode='test': the imgcorruptlike Spatter corruption of "
+                                  "lib/roi_data_layer/minibatch.py:648-664 is out of scope; pass augment_en=False")
+    if augment_en and not cfg.IMAGE.EN_AUG:
+        raise NotImplementedError("augment_en=True: image augmentation (lib/roi_data_layer/minibatch.py:540-647, "
+                                  "roi_data_layer/image_augment.py) is behind cfg.IMAGE.EN_AUG, which is False; set it "
+                                  "or pass augment_en=False")
 
 
 def _get_image_blob(roidb, im_scale, augment_en=False, mode='train', device='cuda'):
     """minibatch.py:518-676.  ``roidb``: list with ONE filename (mode 'test') or ONE roidb entry (dict with 'filename').
-    Returns (im_infos, blob (1, H', W', 3) float32 device tensor, local_roidb)."""
+    Returns (im_infos, blob (1, H', W', 3) float32 device tensor, local_roidb).  ``augment_en`` (train / val mode, behind
+    cfg.IMAGE.EN_AUG): file -> uint8 frame on the device -> ``frcnn_image_augment`` (skipped for an identity draw) ->
+    ``frcnn_prep_image``; boxes, ``ignore`` and ``flipped`` of the local entry follow on the host."""
     from copy import deepcopy
     from ..utils.blob import im_list_to_blob, prep_im_for_blob
-    _no_augmentation(augment_en)
+    _no_augmentation(augment_en, mode)
     if len(roidb) != 1:
         raise NotImplementedError("single-frame batches only (minibatch.py:111)")
     if mode == 'test':
@@ -101,6 +110,13 @@ def _get_image_blob(roidb, im_scale, augment_en=False, mode='train', device='cud
     else:
         im, local_roidb = read_image_file(roidb[0]['filename']), deepcopy(roidb)
         local_roidb[0]['flipped'] = False
+    if augment_en:
+        from .image_augment import augment_image_gt_boxes, draw_image_augmentation
+        height, width = int(im.shape[0]), int(im.shape[1])
+        aug = draw_image_augmentation(width, height)
+        if not aug.identity:
+            im = ops.image_augment(torch.from_numpy(im).to(device, non_blocking=True), aug)
+        augment_image_gt_boxes(local_roidb[0], aug, width, height)
     im = prep_im_for_blob(im, cfg.PIXEL_MEANS, cfg.PIXEL_STDDEVS, cfg.PIXEL_ARRANGE, im_scale, device=device)
     info = np.array([0, im.shape[1], 0, im.shape[0], 0, 0, im_scale], dtype=np.float32)          # :670
     return [info], im_list_to_blob([im]), local_roidb
@@ -165,7 +181,7 @@ def get_image_minibatch(roidb, num_classes, augment_en, scale, cnt):
         gt_boxes_dc[:, 0:4] = dc * im_scale
         gt_boxes_dc[:, 4] = 0
     blobs = {'data': im_blob, 'info': info, 'filename': entry['filename'], 'gt_boxes': gt_boxes,
-             'gt_boxes_dc': gt_boxes_dc, 'flipped': False}
+             'gt_boxes_dc': gt_boxes_dc, 'flipped': bool(entry['flipped']) if augment_en else False}
     return blobs if len(gt_boxes) else None
 
 

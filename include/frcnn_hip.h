@@ -435,6 +435,43 @@ int frcnn_lidar_augment(const float* points, int num_points, int point_stride, c
                         const float* params_host, uint32_t seed, const uint32_t* seed_dev, float* out, int* kept_count,
                         int max_blocks, void* stream);
 
+/* Image augmentation (lib/roi_data_layer/minibatch.py:540-647), the pixel side of the imgaug block in front of
+ * frcnn_prep_image: img / out are uint8 (h, w, 3) frames in cv2.imread order.  flip = 1 mirrors the frame left-right first
+ * (:549; folded into the first stage's read).  Then num_stages <= FRCNN_IMG_MAX_STAGES stages run in the given order, one
+ * launch each, every one uint8 -> uint8 (round half to even, clip); stage k reads stage_codes_host[k] and the
+ * FRCNN_IMG_NUM_PARAMS floats at stage_params_host + k * FRCNN_IMG_NUM_PARAMS (unused slots 0):
+ *   GAUSS    (:567)     [taps (5, 7 or 9), tap 0 .. tap taps-1]   separable, normalised taps computed by the caller
+ *   AVERAGE  (:568)     [k (2 or 3)]                              k = 1 is the identity: do not pass it
+ *   MEDIAN   (:569)     []                                        3x3; k = 1 is the identity
+ *   SHARPEN  (:570)     [centre weight (1-a) + a(8+l), neighbour weight -a]
+ *   NOISE    (:572-575) [scale]                                   normal01 streams 40, 41, 42 = channel 0, 1, 2; index = pixel
+ *   HUE_SAT  (:576)     [hue offset on the 0..180 circle, saturation offset on 0..255]   memory channel 0 is taken as R
+ *   AFFINE   (:579-586) [m0 .. m5 (output -> source: xs = m0 x + m1 y + m2, ys = m3 x + m4 y + m5), order (0 nearest,
+ *                        1 bilinear), border value]
+ *   DROPOUT  (:587)     [p, per_channel (0 / 1)]                  uniform01 stream 86; index = pixel, or pixel * 3 + channel
+ * Draws are counter-based, value = f(seed + *seed_dev, stream, index) (csrc/rng.h; seed_dev device uint32 or NULL).
+ * num_stages == 0: a (mirrored) copy.  scratch (frcnn_image_augment_ws_bytes(h, w) bytes, device) is the ping-pong buffer,
+ * read only when num_stages > 1 (may be NULL otherwise).  img, out and scratch must not overlap one another: rejected.
+ * debug_pre (device, h*w*3 floats, usually NULL): with exactly one NOISE or HUE_SAT stage, the values before rounding.
+ * No allocation, no host synchronisation; kernel launches only, so a stream capture holds kernel nodes.
+ * Operators restated from the published algorithms of imgaug / cv2 / scikit-image (absent: parity unpinned); the
+ * conventions are listed in csrc/image_augment.hip. */
+#define FRCNN_IMG_COPY 0
+#define FRCNN_IMG_GAUSS 1
+#define FRCNN_IMG_AVERAGE 2
+#define FRCNN_IMG_MEDIAN 3
+#define FRCNN_IMG_SHARPEN 4
+#define FRCNN_IMG_NOISE 5
+#define FRCNN_IMG_HUE_SAT 6
+#define FRCNN_IMG_AFFINE 7
+#define FRCNN_IMG_DROPOUT 8
+#define FRCNN_IMG_MAX_STAGES 8
+#define FRCNN_IMG_NUM_PARAMS 12
+size_t frcnn_image_augment_ws_bytes(int h, int w);
+int frcnn_image_augment(const uint8_t* img_hwc3, int h, int w, int flip, int num_stages, const int* stage_codes_host,
+                        const float* stage_params_host, uint32_t seed, const uint32_t* seed_dev, void* scratch,
+                        size_t scratch_bytes, uint8_t* out, float* debug_pre, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training path (BASELINE config 4: FPN forward + backward of one train_step, lib/model/train_val.py:458)
  * ------------------------------------------------------------------------------------------- */
