@@ -88,6 +88,8 @@ PROTOTYPES = {
                                    c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "frcnn_lidar_augment": (c_int, [_P, c_int, c_int, POINTER(c_float), ctypes.c_uint, POINTER(c_float), c_uint32, _P, _P, _P,
                                     c_int, _P]),
+    "frcnn_lidar_augment_fov": (c_int, [_P, c_int, c_int, POINTER(c_float), ctypes.c_uint, POINTER(c_float), c_uint32, _P, _P,
+                                        _P, c_int, POINTER(c_double), c_int, c_int, _P]),
     "frcnn_image_augment_ws_bytes": (c_size_t, [c_int, c_int]),
     "frcnn_image_augment": (c_int, [_P, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_float), c_uint32, _P, _P, c_size_t,
                                     _P, _P, _P]),

@@ -2,6 +2,10 @@
 // per-point transforms the reference applies in numpy between reading a scan and voxelising it, as ONE pass, one
 // thread per point, in the reference's order:
 //
+//  -1. camera field of view of KITTI / CADC scans (:251-268,678-693; frcnn_lidar_augment_fov only): in double,
+//      h = M [x y z 1]^T, u = h0 / h2, v = h1 / h2, keep iff 0 <= u < img_w and 0 <= v < img_h.  The quotient is formed
+//      (not multiplied through by h2) and there is no depth test, like get_fov_flag: a point BEHIND the camera whose
+//      quotient lands inside the frame is kept; h2 == 0 and NaN / Inf coordinates fail the comparisons and are dropped.
 //   0. filter_points on the raw point (:232-235,274): a point outside cfg.LIDAR.*_RANGE is dropped before any transform
 //   1. Gaussian distortion (:309-319)            x += sx*n0, y += sy*n1, z += sz*n2
 //   2. dropout (:321-325)                        keep iff u < p_keep
@@ -13,10 +17,11 @@
 //                                                intensity *= delta, keep iff rho/(r^2 + eps)*delta >= rho/(pi r_max^2)
 //   7. test-time dropout (:422-425)              keep iff u < 0.8
 //
-// Every draw is a pure function of (seed, stream, row index of the point) (rng.h), so the launch does not depend on the
-// grid shape and the CPU oracle replays it.  A dropped point KEEPS ITS ROW: x, y, z become NaN.  The voxeliser's range
-// test (voxelize.hip, vox_cell_kernel) rejects NaN, and voxel numbering / the first-max_points rule only look at
-// surviving points in ascending row order, so this equals the reference's order-preserving compaction without a scan.
+// Every draw is a pure function of (seed, stream, row index of the point IN THE FILE) (rng.h), so the launch does not
+// depend on the grid shape, nor on how many points the field-of-view step removed, and the CPU oracle replays it.
+// A dropped point KEEPS ITS ROW: x, y, z become NaN.  The voxeliser's range test (voxelize.hip, vox_cell_kernel)
+// rejects NaN, and voxel numbering / the first-max_points rule only look at surviving points in ascending row order,
+// so this equals the reference's order-preserving compaction (the reference's points[fov_flag] too) without a scan.
 // The surviving points that also pass the reference's final filter_points (:426) are counted (one atomic per
 // workgroup) so the host can skip a frame without points (:428-432).
 // Compiled with -ffp-contract=off: each product and sum above rounds once, like the numpy expression it restates.
@@ -48,6 +53,22 @@ struct AugParams {
   float rain_sigma_k, rain_att_k, rain_rho, rain_p_min, test_p_keep;
   int n, f;
 };
+
+// camera of the field-of-view step: row-major 3x4 M (LiDAR point -> homogeneous pixel) and the frame size, all double
+struct FovParams {
+  double m[12];
+  double img_w, img_h;
+};
+
+// get_fov_flag (:678-693) on one point.  Each product and sum rounds once (no fma: -ffp-contract=off), the divisions stay.
+__device__ __forceinline__ bool in_fov(const FovParams& c, float xf, float yf, float zf) {
+  const double x = xf, y = yf, z = zf;
+  const double h0 = ((c.m[0] * x + c.m[1] * y) + c.m[2] * z) + c.m[3];
+  const double h1 = ((c.m[4] * x + c.m[5] * y) + c.m[6] * z) + c.m[7];
+  const double h2 = ((c.m[8] * x + c.m[9] * y) + c.m[10] * z) + c.m[11];
+  const double u = h0 / h2, v = h1 / h2;
+  return u >= 0.0 && u < c.img_w && v >= 0.0 && v < c.img_h;             // NaN / +-Inf quotients fail
+}
 
 __device__ __forceinline__ bool in_range(const AugParams& p, float x, float y, float z) {
   return x >= p.lo[0] && y >= p.lo[1] && z >= p.lo[2] && x < p.hi[0] && y < p.hi[1] && z < p.hi[2];
@@ -88,9 +109,13 @@ __device__ __forceinline__ bool augment_point(const AugParams& p, uint32_t seed,
   return true;
 }
 
+struct NoFov {};
+__device__ __forceinline__ bool in_fov(const NoFov&, float, float, float) { return true; }
+
 // VEC4: rows of exactly four floats, both pointers 16-byte aligned -> one 16-byte load and store per point.
-template <bool VEC4>
-__global__ __launch_bounds__(256) void frcnn_lidar_augment_kernel(const float* in, AugParams p, uint32_t seed,
+// Cam = FovParams: the field-of-view step runs first; Cam = NoFov: the step and its arguments are compiled out.
+template <bool VEC4, typename Cam>
+__global__ __launch_bounds__(256) void frcnn_lidar_augment_kernel(const float* in, AugParams p, Cam cam, uint32_t seed,
                                                                  const uint32_t* __restrict__ seed_dev, float* out,
                                                                  int* __restrict__ kept) {   // out may be `in` (in place)
   if (seed_dev) seed += *seed_dev;      // per-frame seed from device memory (a replayed hipGraph keeps `seed` itself)
@@ -105,7 +130,7 @@ __global__ __launch_bounds__(256) void frcnn_lidar_augment_kernel(const float* i
       const float* q = in + (size_t)i * p.f;
       x = q[0]; y = q[1]; z = q[2]; w = q[3];
     }
-    const bool keep = augment_point(p, seed, (uint32_t)i, x, y, z, w);
+    const bool keep = in_fov(cam, x, y, z) && augment_point(p, seed, (uint32_t)i, x, y, z, w);
     if (!keep) x = y = z = nan;
     alive += keep && in_range(p, x, y, z);                    // the reference's second filter_points (:426)
     if (VEC4) {
@@ -128,12 +153,21 @@ __global__ __launch_bounds__(256) void frcnn_lidar_augment_kernel(const float* i
   }
 }
 
-}  // namespace
+template <typename Cam>
+void launch(unsigned blocks, bool vec4, hipStream_t stream, const float* points, const AugParams& p, const Cam& cam,
+            uint32_t seed, const uint32_t* seed_dev, float* out, int* kept_count) {
+  if (vec4)
+    hipLaunchKernelGGL((frcnn_lidar_augment_kernel<true, Cam>), dim3(blocks), dim3(256), 0, stream, points, p, cam, seed,
+                       seed_dev, out, kept_count);
+  else
+    hipLaunchKernelGGL((frcnn_lidar_augment_kernel<false, Cam>), dim3(blocks), dim3(256), 0, stream, points, p, cam, seed,
+                       seed_dev, out, kept_count);
+}
 
-extern "C" int frcnn_lidar_augment(const float* points, int num_points, int point_stride, const float* range_host,
-                                   unsigned flags, const float* params_host, uint32_t seed, const uint32_t* seed_dev,
-                                   float* out, int* kept_count, int max_blocks, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+// both entries; proj_host == nullptr: no field-of-view step
+int lidar_augment(const float* points, int num_points, int point_stride, const float* range_host, unsigned flags,
+                  const float* params_host, uint32_t seed, const uint32_t* seed_dev, float* out, int* kept_count,
+                  int max_blocks, const double* proj_host, int img_h, int img_w, hipStream_t stream) {
   FRCNN_REQUIRE(points && range_host && params_host && out && kept_count, "lidar_augment: null argument");
   FRCNN_REQUIRE(num_points > 0 && point_stride >= 4,
                 "lidar_augment: bad arguments (points are num_points > 0 rows of >= 4 floats x,y,z,intensity)");
@@ -176,17 +210,43 @@ extern "C" int frcnn_lidar_augment(const float* points, int num_points, int poin
   p.test_p_keep = 0.8f;
   p.n = num_points;
   p.f = point_stride;
+  FovParams cam = {};
+  if (proj_host) {
+    FRCNN_REQUIRE(img_h > 0 && img_w > 0, "lidar_augment_fov: image size %d x %d", img_h, img_w);
+    for (int j = 0; j < 12; ++j) {
+      FRCNN_REQUIRE(std::isfinite(proj_host[j]), "lidar_augment_fov: projection entry %d is not finite", j);
+      cam.m[j] = proj_host[j];
+    }
+    cam.img_w = img_w;
+    cam.img_h = img_h;
+  }
   hipError_t e = fill_bytes(kept_count, 0, sizeof(int), stream);
   if (e != hipSuccess) return fail(FRCNN_ERR_LAUNCH, "lidar_augment: memset: %s", hipGetErrorString(e));
   unsigned blocks = (unsigned)std::min<size_t>(((size_t)num_points + 255) / 256, LA_MAX_BLOCKS);
   if (max_blocks > 0) blocks = std::min<unsigned>(blocks, (unsigned)max_blocks);
   const bool vec4 = point_stride == 4 && (reinterpret_cast<uintptr_t>(points) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  if (vec4)
-    hipLaunchKernelGGL(frcnn_lidar_augment_kernel<true>, dim3(blocks), dim3(256), 0, stream, points, p, seed, seed_dev, out,
-                       kept_count);
+  if (proj_host)
+    launch(blocks, vec4, stream, points, p, cam, seed, seed_dev, out, kept_count);
   else
-    hipLaunchKernelGGL(frcnn_lidar_augment_kernel<false>, dim3(blocks), dim3(256), 0, stream, points, p, seed, seed_dev, out,
-                       kept_count);
+    launch(blocks, vec4, stream, points, p, NoFov{}, seed, seed_dev, out, kept_count);
   return check_launch("frcnn_lidar_augment_kernel");
+}
+
+}  // namespace
+
+extern "C" int frcnn_lidar_augment(const float* points, int num_points, int point_stride, const float* range_host,
+                                   unsigned flags, const float* params_host, uint32_t seed, const uint32_t* seed_dev,
+                                   float* out, int* kept_count, int max_blocks, void* stream) {
+  return lidar_augment(points, num_points, point_stride, range_host, flags, params_host, seed, seed_dev, out, kept_count,
+                       max_blocks, nullptr, 0, 0, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int frcnn_lidar_augment_fov(const float* points, int num_points, int point_stride, const float* range_host,
+                                       unsigned flags, const float* params_host, uint32_t seed, const uint32_t* seed_dev,
+                                       float* out, int* kept_count, int max_blocks, const double* proj_host, int img_h,
+                                       int img_w, void* stream) {
+  FRCNN_REQUIRE(proj_host, "lidar_augment_fov: null projection matrix");
+  return lidar_augment(points, num_points, point_stride, range_host, flags, params_host, seed, seed_dev, out, kept_count,
+                       max_blocks, proj_host, img_h, img_w, static_cast<hipStream_t>(stream));
 }

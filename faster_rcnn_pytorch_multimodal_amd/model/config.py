@@ -105,8 +105,9 @@ def _defaults():
                    EN_AUG_AFFINE=True, EN_AUG_DROPOUT=True)
     # sensor range in metres, read by the rain simulation as cfg[cfg.DB_NAME.upper()].LIDAR_MAX_RANGE (config.py:431-449)
     c.WAYMO = dict(LIDAR_MAX_RANGE=200)
-    c.KITTI = dict(LIDAR_MAX_RANGE=120)
-    c.CADC = dict(LIDAR_MAX_RANGE=200)
+    # IMG_SIZE [height, width] of the front camera: the frame of the field-of-view filter (config.py:442,447)
+    c.KITTI = dict(LIDAR_MAX_RANGE=120, IMG_SIZE=[375, 1242])
+    c.CADC = dict(LIDAR_MAX_RANGE=200, IMG_SIZE=[624, 1280])
     return c
 
 

@@ -810,14 +810,29 @@ AUG_STREAM = {'gauss_x': 32, 'gauss_y': 33, 'gauss_z': 34, 'rain': 35, 'dropout'
               'image_noise_0': 40, 'image_noise_1': 41, 'image_noise_2': 42, 'image_dropout': 86}
 
 
-def lidar_augment_points(points, params, seed, pc_extents, seed_dev=None, out=None, max_blocks=0):
+def _fov_arguments(proj, img_size):
+    """(double[12] row-major M, img_h, img_w) of ``proj`` (3x4, anything numpy reads) and ``img_size`` = [height, width]."""
+    import numpy as np
+    m = np.asarray(proj, dtype=np.float64)
+    if m.shape != (3, 4):
+        raise _hip.HipError("proj must be a 3x4 matrix (roi_data_layer.lidar_calib), got shape %s" % (m.shape,))
+    if img_size is None or len(img_size) != 2:
+        raise _hip.HipError("img_size must be [height, width] (cfg.<DB_NAME>.IMG_SIZE), got %r" % (img_size,))
+    return (ctypes.c_double * 12)(*[float(v) for v in m.reshape(-1)]), int(img_size[0]), int(img_size[1])
+
+
+def lidar_augment_points(points, params, seed, pc_extents, seed_dev=None, out=None, max_blocks=0, proj=None, img_size=None):
     """Per-point LiDAR augmentation / rain simulation in front of ``bev_voxelize`` (frcnn_lidar_augment;
     lib/roi_data_layer/minibatch.py:274-428).  ``points`` (N, F>=4) device tensor; ``params``: the decision record
     (``roi_data_layer.lidar_augment.LidarAugment`` or any object with its fields: flip_x, flip_y, gauss (sx, sy, sz) or
     None, p_keep or None, rotation (radians) or None, swap_xy, rain_rate or None, rain_max_range, test_dropout);
     ``pc_extents`` = [X0, Y0, Z0, X1, Y1, Z1].  Returns (points_out, kept_count): dropped rows carry NaN in x, y, z,
-    kept_count is a one-element int32 device tensor (surviving points inside the extents).  ``out=points`` works in place."""
+    kept_count is a one-element int32 device tensor (surviving points inside the extents).  ``out=points`` works in place.
+    ``proj`` (3x4 float64, ``roi_data_layer.lidar_calib``) with ``img_size`` = [height, width]: the camera field-of-view
+    filter of KITTI / CADC scans (:251-268,678-693) runs as the first step of the same pass (frcnn_lidar_augment_fov)."""
     import math
+    if (proj is None) != (img_size is None):
+        raise _hip.HipError("lidar_augment_points: proj and img_size go together")
     lib = _hip.load()
     _dev_f32(points, "points")
     if points.dim() != 2 or points.shape[1] < 4 or points.shape[0] == 0:
@@ -842,10 +857,35 @@ def lidar_augment_points(points, params, seed, pc_extents, seed_dev=None, out=No
     flags |= (AUG_SWAP_XY if params.swap_xy else 0) | (AUG_FLIP_Y if params.flip_y else 0)
     flags |= (AUG_FLIP_X if params.flip_x else 0) | (AUG_TEST_DROPOUT if params.test_dropout else 0)
     kept = torch.empty((1,), dtype=torch.int32, device=points.device)
+    if proj is not None:
+        m, img_h, img_w = _fov_arguments(proj, img_size)
+        _hip.check(lib.frcnn_lidar_augment_fov(_ptr(points), points.shape[0], points.shape[1], _hip.float_array(pc_extents),
+                                               flags, _hip.float_array(vals), int(seed) & 0xFFFFFFFF, _seed_dev(seed_dev),
+                                               _ptr(out), _ptr(kept), int(max_blocks), m, img_h, img_w, _stream()),
+                   "frcnn_lidar_augment_fov")
+        return out, kept
     _hip.check(lib.frcnn_lidar_augment(_ptr(points), points.shape[0], points.shape[1], _hip.float_array(pc_extents), flags,
                                        _hip.float_array(vals), int(seed) & 0xFFFFFFFF, _seed_dev(seed_dev), _ptr(out),
                                        _ptr(kept), int(max_blocks), _stream()), "frcnn_lidar_augment")
     return out, kept
+
+
+class _NoAugmentation:
+    """The identity decision record (the fields ``lidar_augment_points`` reads)."""
+    flip_x = flip_y = swap_xy = test_dropout = False
+    gauss = p_keep = rotation = rain_rate = None
+    rain_max_range = 0.0
+
+
+def lidar_fov_filter(points, proj, img_size, out=None, max_blocks=0):
+    """Camera field-of-view filter of a KITTI / CADC scan alone (frcnn_lidar_augment_fov with every other step off and the
+    range wide open; lib/roi_data_layer/minibatch.py:251-268,678-693).  ``points`` (N, F>=4) device tensor, ``proj`` the
+    3x4 float64 LiDAR -> pixel matrix of ``roi_data_layer.lidar_calib``, ``img_size`` = [height, width].  Returns
+    (points_out, kept): rows that project outside the frame carry NaN in x, y, z (columns 3.. untouched), every other row
+    is the input row; kept is a one-element int32 device tensor (points inside the frame)."""
+    inf = float("inf")
+    return lidar_augment_points(points, _NoAugmentation, 0, [-inf, -inf, -inf, inf, inf, inf], out=out,
+                                max_blocks=max_blocks, proj=proj, img_size=img_size)
 
 
 # frcnn_image_augment: stage codes and the parameter slots per stage of include/frcnn_hip.h

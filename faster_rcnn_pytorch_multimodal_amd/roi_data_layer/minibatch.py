@@ -1,8 +1,8 @@
 """LiDAR input producer - counterpart of ``_get_lidar_blob`` (lib/roi_data_layer/minibatch.py:237-516) for ONE frame
 whose points are already in memory: range filter (:232-235), voxelisation and the BEV scatter (:434-512) run as
 ``frcnn_bev_voxelize`` on the device, the per-point augmentations and the test-time rain simulation in front of them
-(:274-428) as ``frcnn_lidar_augment``; file parsing and FOV calibration (:250-273) stay with the caller (dataset
-plumbing, out of scope).  Returns the same ``(infos, blob)`` the reference's data layer hands to
+(:274-428) as ``frcnn_lidar_augment``; the caller parses the file and, for a KITTI / CADC scan, applies the camera
+field-of-view filter (:250-273; ``_get_lidar_blob`` below does both).  Returns the same ``(infos, blob)`` the reference's data layer hands to
 ``Network.forward``: blob (1, num_y_voxel, num_x_voxel, cfg.LIDAR.NUM_CHANNEL) NHWC on the device,
 info = [0, num_x_voxel, 0, num_y_voxel, 0, NUM_SLICES, scale].
 
@@ -11,6 +11,9 @@ The reference-named entry points (``_get_image_blob``, ``_get_lidar_blob``, ``ge
 device producers (``frcnn_prep_image``, ``frcnn_lidar_augment``, ``frcnn_bev_voxelize``).  LiDAR frames: ``augment_en=True``
 draws the reference's flips / distortion / dropout / rotation / swap per frame (``roi_data_layer/lidar_augment.py``),
 moves the points on the device and the gt boxes on the host; ``mode='test'`` applies cfg.TEST.RAIN_SIM_EN / DROPOUT_EN.
+KITTI / CADC ``.bin`` scans (``cfg.DB_NAME``) are first cut to the front camera's field of view (:251-268,678-693): the
+calibration file is read on the host (``roi_data_layer/lidar_calib.py``), the projection and the test run on the device
+as the first step of the same per-point pass (``frcnn_lidar_augment_fov``).
 Image frames: with ``cfg.IMAGE.EN_AUG`` on, ``augment_en=True`` draws the reference's flip / blur-sharpen / noise /
 hue-saturation / affine / dropout per frame (``roi_data_layer/image_augment.py``, minibatch.py:540-647), runs the pixels
 through ``frcnn_image_augment`` on the device in front of ``frcnn_prep_image`` and moves, clips and flags the gt boxes on
@@ -74,11 +77,9 @@ def read_image_file(filename):
 
 def read_point_cloud_file(filename):
     """(N, >=4) float32 rows [x, y, z, intensity, ...]: ``.bin`` = flat float32 quadruples, ``.npy`` as stored
-    (minibatch.py:251-270).  The KITTI / CADC field-of-view filters need the datasets' calibration files (out of scope)."""
+    (minibatch.py:251-270).  The raw rows of the file whatever the dataset: the camera field-of-view filter of KITTI /
+    CADC scans (:253-264) runs on the device afterwards (``_get_lidar_blob``)."""
     if '.bin' in str(filename):
-        if cfg.DB_NAME in ('kitti', 'cadc'):
-            raise NotImplementedError("camera field-of-view filtering of %s scans needs the dataset's calibration tooling"
-                                      % cfg.DB_NAME)
         return np.fromfile(filename, dtype=np.float32).reshape(-1, 4)
     if '.npy' in str(filename):
         return np.load(filename)
@@ -126,8 +127,13 @@ def _get_lidar_blob(roidb, pc_extents, scale, augment_en=False, mode='train', de
     """minibatch.py:237-516: file -> points -> augmentation / rain simulation (``frcnn_lidar_augment``, only when a step
     is switched on) -> ``get_lidar_blob`` (range filter, voxel generator and BEV scatter on the device).  ``pc_extents`` is
     what the reference passes (cfg.LIDAR.*_RANGE); the voxeliser reads the same ranges from cfg.  Waymo scans carry the
-    elongation in column 4 (:496-499).  Returns (infos, None, local_roidb) when no point is left (:428-432)."""
+    elongation in column 4 (:496-499).  A ``.bin`` scan with cfg.DB_NAME 'kitti' or 'cadc' goes through the camera
+    field-of-view filter first (:253-264), in the same launch as the augmentation (``frcnn_lidar_augment_fov``; with no
+    step switched on, that launch is the filter alone); its calibration file is derived from the scan's path like the
+    reference does, or named by the roidb entry's optional 'calib' key.  The gt boxes are not touched by the filter.
+    Returns (infos, None, local_roidb) when no point is left (:428-432)."""
     from copy import deepcopy
+    from .lidar_calib import FOV_DATASETS, frame_projection
     from .lidar_augment import augment_gt_boxes, draw_lidar_augmentation
     if len(roidb) != 1:
         raise NotImplementedError("single-frame batches only (minibatch.py:111)")
@@ -148,7 +154,20 @@ def _get_lidar_blob(roidb, pc_extents, scale, augment_en=False, mode='train', de
         raise ValueError("pc_extents %s differ from cfg.LIDAR.*_RANGE %s" % (list(pc_extents), expected))
     points = read_point_cloud_file(filen)
     elongation = 4 if (cfg.DB_NAME == 'waymo' and points.shape[1] > 4) else None
-    if augment_en or (mode == 'test' and (cfg.TEST.RAIN_SIM_EN or cfg.TEST.DROPOUT_EN)):
+    if cfg.DB_NAME in FOV_DATASETS and '.bin' in str(filen):
+        proj, img_size = frame_projection(filen, None if local_roidb is None else local_roidb[0])
+        aug = draw_lidar_augmentation(augment_en=augment_en, mode=mode)             # the identity record: the filter alone
+        if points.shape[0] == 0:
+            return [], None, local_roidb
+        points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(device, non_blocking=True)
+        points, kept = ops.lidar_augment_points(points, aug, aug.seed, expected, out=points, proj=proj, img_size=img_size)
+        if local_roidb is not None and not aug.identity:
+            augment_gt_boxes(local_roidb[0], aug)
+        if int(kept.item()) <= 0:                                                    # :428-432
+            print('No PC points in frame {} FLIP_X: {} FLIP_Y: {} ROT: {} SWAP_X_Y: {}'.format(
+                filen, aug.flip_x, aug.flip_y, aug.rotation is not None, aug.swap_xy))
+            return [], None, local_roidb
+    elif augment_en or (mode == 'test' and (cfg.TEST.RAIN_SIM_EN or cfg.TEST.DROPOUT_EN)):
         aug = draw_lidar_augmentation(augment_en=augment_en, mode=mode)
         if not aug.identity:
             if points.shape[0] == 0:

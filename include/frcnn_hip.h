@@ -434,6 +434,21 @@ int frcnn_bev_voxelize(const float* points, int num_points, int point_stride, co
 int frcnn_lidar_augment(const float* points, int num_points, int point_stride, const float* range_host, unsigned flags,
                         const float* params_host, uint32_t seed, const uint32_t* seed_dev, float* out, int* kept_count,
                         int max_blocks, void* stream);
+/* The same pass with the camera field-of-view filter of KITTI / CADC scans (lib/roi_data_layer/minibatch.py:251-268,
+ * get_fov_flag :678-693) as its FIRST step, in front of filter_points: no launch of its own.  proj_host[12]: row-major
+ * 3x4 double matrix M that takes a homogeneous LiDAR point to the homogeneous pixel (KITTI: P2 [R0 0; 0 1] [Tr; 0 0 0 1];
+ * CADC: the first three rows of K4 inv(T_LIDAR_CAM00); roi_data_layer/lidar_calib.py), entries finite; img_h, img_w > 0 =
+ * cfg.<DB>.IMG_SIZE.  Per point, in double: h = M [x y z 1]^T, u = h0 / h2, v = h1 / h2 (the DIVISION, like the
+ * reference), keep iff 0 <= u < img_w and 0 <= v < img_h.  No depth test, like the reference: a point behind the camera
+ * whose quotient lands inside the frame is kept; h2 == 0 and NaN / Inf coordinates fail the comparisons (as in numpy) and
+ * are dropped.  A rejected point keeps its row with x, y, z = NaN, columns 3.. untouched.  The draws of the later steps
+ * stay indexed by the row in the FILE, so a frame's draws do not depend on how many points the filter removed:
+ * the call equals the filter alone (flags 0) followed by frcnn_lidar_augment with the same flags, parameters and seed,
+ * bit for bit, kept_count included.  kept_count keeps its meaning (survivors inside range_host after all steps).
+ * No allocation, no host synchronisation; kernel launches only. */
+int frcnn_lidar_augment_fov(const float* points, int num_points, int point_stride, const float* range_host, unsigned flags,
+                            const float* params_host, uint32_t seed, const uint32_t* seed_dev, float* out, int* kept_count,
+                            int max_blocks, const double* proj_host, int img_h, int img_w, void* stream);
 
 /* Image augmentation (lib/roi_data_layer/minibatch.py:540-647), the pixel side of the imgaug block in front of
  * frcnn_prep_image: img / out are uint8 (h, w, 3) frames in cv2.imread order.  flip = 1 mirrors the frame left-right first
