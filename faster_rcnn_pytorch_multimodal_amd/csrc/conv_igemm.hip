@@ -36,6 +36,7 @@
 #include <array>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 
 namespace {
@@ -1255,33 +1256,168 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue(const float* __restr
   }
 }
 
-// Workgroup configurations: block tile (64*tm) x (64*tn) = (32*TM*WM) x (32*TN*WN).
-struct TileCfg {
-  int tm, tn;          // block tile in units of 64 pixels x 64 channels (the frcnn_conv2d_set_tile key)
-  int wm, wn, wtm, wtn;  // wave grid and 32x32 tiles per wave
+// ---- per-dispatch timing (frcnn_conv2d_profile_begin / _end) -----------------------------------------------------------
+// While a profile is open every kernel of frcnn_conv2d_fwd is launched through hipExtLaunchKernelGGL with its own
+// start / stop events: the pair brackets THAT dispatch on the launch stream (begin -> end of the kernel, the quantity
+// rocprofv3 --kernel-trace reports), without the event-packet overhead two separately recorded events add around a
+// launch.  bench.py's `roofline` is computed from these durations.
+struct ProfRec {
+  hipEvent_t e0, e1;
+  int call, kind;      // frcnn_conv2d_fwd call number since profile_begin; kind 0 = main kernel, 1 = split-K second pass
 };
+std::vector<ProfRec> g_prof;
+std::atomic<bool> g_prof_on{false};
+int g_prof_call = -1;
+
+bool prof_events(int kind, hipEvent_t* e0, hipEvent_t* e1, hipStream_t stream) {
+  if (!g_prof_on) return false;
+  // a capturing stream cannot take the timed launch form (events would become graph nodes): plain launch, no record
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return false;
+  if (hipEventCreate(e0) != hipSuccess) return false;
+  if (hipEventCreate(e1) != hipSuccess) { (void)hipEventDestroy(*e0); return false; }
+  g_prof.push_back(ProfRec{*e0, *e1, g_prof_call, kind});
+  return true;
+}
+
+// ---- launching ---------------------------------------------------------------------------------------------------------
+// The one launcher of this file's kernels: the once-per-kernel dynamic-LDS attribute (kernels that ask for LDS at launch
+// may need more than the 64 KB granted by default), the timed launch form while a profile is open (`kind` as in ProfRec)
+// and the launch check.  `args` must have the kernel's parameter types exactly (hipExtLaunchKernelGGL deduces from them).
+template <auto Kernel, typename... Args>
+int launch_kernel(const char* name, int kind, dim3 grid, unsigned block, size_t lds, hipStream_t stream, Args... args) {
+  static std::atomic<bool> configured{false};   // idempotent attribute call: a race only repeats it
+  if (lds > 0 && !configured) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv: set LDS size: %s", hipGetErrorString(e));
+    configured = true;
+  }
+  hipEvent_t e0, e1;
+  if (prof_events(kind, &e0, &e1, stream)) hipExtLaunchKernelGGL(Kernel, grid, dim3(block), (uint32_t)lds, stream, e0, e1, 0, args...);
+  else hipLaunchKernelGGL(Kernel, grid, dim3(block), lds, stream, args...);
+  return frcnn::check_launch(name);
+}
+
+// One thin wrapper per kernel family of the implicit GEMM: its LDS bytes, its block size and, for the persistent kernel,
+// its grid and two extra arguments.  p.tiles_m / tiles_n are set by launch_gemm.
+typedef int (*ConvLaunch)(const ConvParams& p, int splits, int groups, hipStream_t stream);
+dim3 tile_grid(const ConvParams& p, int splits, int groups) { return dim3(p.tiles_m * p.tiles_n, groups, splits); }
+
+template <int WM, int WN, int TM, int TN, bool ALIGNED, bool WINO = false>
+int launch_reg(const ConvParams& p, int splits, int groups, hipStream_t stream) {   // register-staged, two stages of padded rows
+  constexpr size_t lds = (size_t)2 * 32 * (TM * WM + TN * WN) * LDS_PITCH * sizeof(float);
+  return launch_kernel<conv_igemm_f32<WM, WN, TM, TN, ALIGNED, WINO>>("conv_igemm_f32", 0, tile_grid(p, splits, groups), 64 * WM * WN,
+                                                                      lds, stream, p);
+}
+template <int WM, int WN>
+int launch_dma(const ConvParams& p, int splits, int groups, hipStream_t stream) {   // LDS-DMA, three stages, 8 waves of 2x2 tiles
+  constexpr size_t lds = (size_t)3 * 64 * (WM + WN) * 32 * sizeof(float);
+  return launch_kernel<conv_igemm_dma_f32<WM, WN>>("conv_igemm_dma_f32", 0, tile_grid(p, splits, groups), 512, lds, stream, p);
+}
+int launch_dma2(const ConvParams& p, int splits, int groups, hipStream_t stream) {   // LDS-DMA, two stages, 128x128
+  constexpr size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
+  return launch_kernel<conv_igemm_dma2_f32<2, 2>>("conv_igemm_dma2_f32", 0, tile_grid(p, splits, groups), 256, lds, stream, p);
+}
+template <int WM, int WN, int TM, int TN>
+int launch_buf(const ConvParams& p, int splits, int groups, hipStream_t stream) {   // LDS-DMA through buffer loads, three stages
+  constexpr size_t lds = (size_t)3 * 32 * (TM * WM + TN * WN) * 32 * sizeof(float);
+  return launch_kernel<conv_igemm_buf_f32<WM, WN, TM, TN>>("conv_igemm_buf_f32", 0, tile_grid(p, splits, groups), 64 * WM * WN, lds,
+                                                           stream, p);
+}
+int launch_pbuf(const ConvParams& p, int splits, int groups, hipStream_t stream) {   // the same, 64x64, persistent workgroups
+  constexpr size_t lds = ((size_t)3 * (64 + 64) * 32 + (size_t)4 * 32 * LDS_PITCH) * sizeof(float);
+  const long total = (long)p.tiles_m * p.tiles_n * groups * splits;
+  const dim3 grid((unsigned)std::min<long>(total, 2L * NUM_CU));      // two resident workgroups per CU (66 KB of LDS each)
+  return launch_kernel<conv_igemm_pbuf_f32>("conv_igemm_pbuf_f32", 0, grid, 256, lds, stream, p, groups, splits);
+}
+
+// ---- plan tiles --------------------------------------------------------------------------------------------------------
+// A plan names its kernel by an index into kTiles.  The indices are the serialised form of plan tables (frcnn_conv2d_export_plans),
+// so rows are appended, never moved.  A row: the block tile (64*tm) x (64*tn) = (32*WTM*WM) x (32*WTN*WN), its register-staged
+// kernel, and up to two alternatives tried in order when C % 32 == 0 - the first one whose staging-mode set holds the current
+// frcnn_conv2d_set_staging mode and whose operand bound is met runs instead of the register-staged kernel (resolve_tile).
+struct TileAlt {
+  ConvLaunch launch;   // nullptr: none
+  unsigned modes;      // bit S: applies in staging mode S
+  bool small;          // needs both operands below 2 GB (the buffer-load kernels: ConvParams::xbytes / wbytes)
+};
+struct TileCfg {
+  int tm, tn;            // block tile in units of 64 pixels x 64 channels (the frcnn_conv2d_set_tile key)
+  int wm, wn, wtm, wtn;  // wave grid and 32x32 tiles per wave
+  ConvLaunch reg[2];     // the register-staged kernel of the tile: [0] any C, [1] C % 32 == 0
+  TileAlt alt[2];
+};
+constexpr unsigned kModes123 = 0xE, kMode2 = 1u << 2, kMode3 = 1u << 3;
+template <int WM, int WN, int TM, int TN>
+constexpr TileCfg tile_row(TileAlt a0, TileAlt a1 = TileAlt{nullptr, 0, false}) {
+  return TileCfg{WM * TM / 2, WN * TN / 2, WM, WN, TM, TN, {launch_reg<WM, WN, TM, TN, false>, launch_reg<WM, WN, TM, TN, true>}, {a0, a1}};
+}
 constexpr TileCfg kTiles[] = {
-    {4, 2, 4, 2, 2, 2},  // 256x128, 8 waves, one workgroup per CU
-    {2, 4, 2, 4, 2, 2},  // 128x256, 8 waves
-    {2, 2, 2, 2, 2, 2},  // 128x128, 4 waves, two workgroups per CU
-    {2, 1, 2, 2, 2, 1},  // 128x64
-    {1, 2, 2, 2, 1, 2},  // 64x128
-    {1, 1, 2, 2, 1, 1},  // 64x64
-    {2, 2, 2, 2, 2, 2},  // 128x128, 4 waves, LDS-DMA with two stages: two workgroups per CU (C % 32 == 0; else as index 2)
-    {1, 1, 2, 2, 1, 1},  // 64x64,  LDS-DMA through buffer loads, three stages (conv_igemm_buf_f32; C % 32 == 0 and < 2 GB operands, else as index 5)
-    {2, 1, 2, 2, 2, 1},  // 128x64, the same kernel (else as index 3)
-    {1, 2, 2, 2, 1, 2},  // 64x128, the same kernel (else as index 4)
-    {2, 2, 2, 2, 2, 2},  // 128x128, the same kernel, 96 KB of LDS: one workgroup per CU (else as index 2)
-    {4, 2, 4, 2, 2, 2},  // 256x128, the same kernel, 8 waves (else as index 0)
-    {2, 4, 2, 4, 2, 2},  // 128x256, the same kernel, 8 waves (else as index 1)
-    {1, 1, 2, 2, 1, 1},  // 64x64, PERSISTENT workgroups walking their tiles as one K-step stream (conv_igemm_pbuf_f32; else as index 7)
+    // 0 .. 5, the six tile shapes - all that choose_plan or a forced tile selects: the buffer-load kernel in staging mode 3, else
+    tile_row<4, 2, 2, 2>({launch_buf<4, 2, 2, 2>, kMode3, true}, {launch_dma<4, 2>, kModes123, false}),  // 256x128, 8 waves, one workgroup per CU: LDS-DMA
+    tile_row<2, 4, 2, 2>({launch_buf<2, 4, 2, 2>, kMode3, true}, {launch_dma<2, 4>, kModes123, false}),  // 128x256, 8 waves: LDS-DMA
+    tile_row<2, 2, 2, 2>({launch_buf<2, 2, 2, 2>, kMode3, true}, {launch_dma2, kMode2, false}),  // 128x128, 4 waves, two workgroups per CU (mode 2: test hook)
+    tile_row<2, 2, 2, 1>({launch_buf<2, 2, 2, 1>, kMode3, true}),     // 128x64
+    tile_row<2, 2, 1, 2>({launch_buf<2, 2, 1, 2>, kMode3, true}),     // 64x128
+    tile_row<2, 2, 1, 1>({launch_buf<2, 2, 1, 1>, kMode3, true}),     // 64x64
+    // 6 .. 13, LDS-DMA variants the autotuner times next to them, in every staging mode but 0
+    tile_row<2, 2, 2, 2>({launch_dma2, kModes123, false}),            // 128x128, two stages: two workgroups per CU
+    tile_row<2, 2, 1, 1>({launch_buf<2, 2, 1, 1>, kModes123, true}),  // 64x64, through buffer loads, three stages
+    tile_row<2, 2, 2, 1>({launch_buf<2, 2, 2, 1>, kModes123, true}),  // 128x64, the same kernel
+    tile_row<2, 2, 1, 2>({launch_buf<2, 2, 1, 2>, kModes123, true}),  // 64x128
+    tile_row<2, 2, 2, 2>({launch_buf<2, 2, 2, 2>, kModes123, true}),  // 128x128, 96 KB of LDS: one workgroup per CU
+    tile_row<4, 2, 2, 2>({launch_buf<4, 2, 2, 2>, kModes123, true}),  // 256x128, 8 waves (else register-staged, unlike index 0)
+    tile_row<2, 4, 2, 2>({launch_buf<2, 4, 2, 2>, kModes123, true}),  // 128x256, 8 waves (likewise, unlike index 1)
+    tile_row<2, 2, 1, 1>({launch_pbuf, kModes123, true}),             // 64x64, PERSISTENT workgroups walking their tiles as one K-step stream
 };
 constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+constexpr int kNumShapes = 6;   // rows 0 .. kNumShapes - 1 hold every tile shape once
+// the rows the code names: the mid-size tile (choose_plan's start, forced Winograd) and the small one (the fall-back of a
+// forced split, the small forced-Winograd GEMM, the ONLY tile of the fused Winograd input transform)
+constexpr int kTile128x128 = 2, kTile64x64 = 5;
+static_assert(kTiles[kTile128x128].tm == 2 && kTiles[kTile128x128].tn == 2 && kTiles[kTile64x64].tm == 1 && kTiles[kTile64x64].tn == 1 &&
+              kTile128x128 < kNumShapes && kTile64x64 < kNumShapes, "the named rows are the register-staged 128x128 and 64x64 tiles");
+
+// the launch function of plan tile `idx`: aligned = C % 32 == 0, staging = the frcnn_conv2d_set_staging mode, small = both operands < 2 GB
+constexpr ConvLaunch resolve_tile(int idx, bool aligned, int staging, bool small) {
+  if (aligned)
+    for (const TileAlt& a : kTiles[idx].alt)
+      if (a.launch && ((a.modes >> staging) & 1) && (small || !a.small)) return a.launch;
+  return kTiles[idx].reg[aligned];
+}
+
+// What every index runs, pinned at compile time.  tile_is: `dflt` with aligned, small operands in the default staging mode 1;
+// the tile's register-staged kernel in staging mode 0 and for every unaligned C.
+template <int WM, int WN, int TM, int TN>
+constexpr bool tile_is(int idx, ConvLaunch dflt) {
+  bool ok = resolve_tile(idx, true, 1, true) == dflt;
+  for (int s = 0; s < 4; ++s)
+    for (int small = 0; small < 2; ++small)
+      ok = ok && resolve_tile(idx, false, s, small) == launch_reg<WM, WN, TM, TN, false> &&
+           resolve_tile(idx, true, 0, small) == launch_reg<WM, WN, TM, TN, true>;
+  return ok;
+}
+static_assert(kNumTiles == 14 && tile_is<4, 2, 2, 2>(0, launch_dma<4, 2>) && tile_is<2, 4, 2, 2>(1, launch_dma<2, 4>) &&
+              tile_is<2, 2, 2, 2>(kTile128x128, launch_reg<2, 2, 2, 2, true>) && tile_is<2, 2, 2, 1>(3, launch_reg<2, 2, 2, 1, true>) &&
+              tile_is<2, 2, 1, 2>(4, launch_reg<2, 2, 1, 2, true>) && tile_is<2, 2, 1, 1>(kTile64x64, launch_reg<2, 2, 1, 1, true>) &&
+              tile_is<2, 2, 2, 2>(6, launch_dma2) && tile_is<2, 2, 1, 1>(7, launch_buf<2, 2, 1, 1>) &&
+              tile_is<2, 2, 2, 1>(8, launch_buf<2, 2, 2, 1>) && tile_is<2, 2, 1, 2>(9, launch_buf<2, 2, 1, 2>) &&
+              tile_is<2, 2, 2, 2>(10, launch_buf<2, 2, 2, 2>) && tile_is<4, 2, 2, 2>(11, launch_buf<4, 2, 2, 2>) &&
+              tile_is<2, 4, 2, 2>(12, launch_buf<2, 4, 2, 2>) && tile_is<2, 2, 1, 1>(13, launch_pbuf),
+              "plan tile indices are serialised (profiles/, exported tables): index -> kernel must stay as listed");
+static_assert(resolve_tile(0, true, 3, true) == launch_buf<4, 2, 2, 2> && resolve_tile(0, true, 3, false) == launch_dma<4, 2> &&
+              resolve_tile(0, true, 1, false) == launch_dma<4, 2> && resolve_tile(kTile128x128, true, 2, false) == launch_dma2 &&
+              resolve_tile(kTile128x128, true, 3, true) == launch_buf<2, 2, 2, 2> &&
+              resolve_tile(kTile128x128, true, 3, false) == launch_reg<2, 2, 2, 2, true> &&
+              resolve_tile(kTile64x64, true, 3, true) == launch_buf<2, 2, 1, 1> && resolve_tile(6, true, 3, false) == launch_dma2 &&
+              resolve_tile(11, true, 1, false) == launch_reg<4, 2, 2, 2, true> && resolve_tile(12, true, 3, false) == launch_reg<2, 4, 2, 2, true> &&
+              resolve_tile(13, true, 2, false) == launch_reg<2, 2, 1, 1, true> && resolve_tile(13, true, 3, true) == launch_pbuf,
+              "fall-backs: index 0 / 1 fall back to LDS-DMA, 11 / 12 to the register-staged kernel");
 
 struct Plan {
   int cfg, splits, steps_per_split;
   int algo = 0;   // 0 = implicit GEMM; 1 = Winograd F(2x2, 3x3) around a grouped GEMM that uses tile `cfg` (splits = 1)
-  int fuse_in = 0;   // algo 1 only: the input transform runs inside the 64x64 GEMM's A-tile load (cfg 5, C % 32 == 0)
+  int fuse_in = 0;   // algo 1 only: the input transform runs inside the 64x64 GEMM's A-tile load (kTile64x64, C % 32 == 0)
 };
 bool winograd_ok(int r, int s, int stride, int pad, int c, int k, int out_stride);
 size_t winograd_ws_bytes(int n, int h, int w, int c, int k);
@@ -1316,7 +1452,7 @@ std::atomic<int> g_force_tm{0}, g_force_tn{0};
 // counts as running one after the other).
 Plan choose_plan(int M, int K, int ksteps, int forced_splits) {
   static const int split_cand[] = {1, 2, 3, 4, 6, 8, 12, 16};
-  Plan best{2, 1, ksteps};
+  Plan best{kTile128x128, 1, ksteps};
   double best_t = 1e300;
   for (int ci = 0; ci < kNumTiles; ++ci) {
     const TileCfg& c = kTiles[ci];
@@ -1346,7 +1482,7 @@ Plan choose_plan(int M, int K, int ksteps, int forced_splits) {
   }
   if (forced_splits > 0 && best_t == 1e300) {
     const int sps = (ksteps + forced_splits - 1) / forced_splits;
-    int ci = 5;   // 64x64
+    int ci = kTile64x64;
     for (int i = kNumTiles - 1; i >= 0; --i)   // first entry with the forced tile (index 6 repeats the 128x128 shape)
       if (g_force_tm > 0 && kTiles[i].tm == g_force_tm && kTiles[i].tn == g_force_tn) ci = i;
     best = Plan{ci, (ksteps + sps - 1) / sps, sps};
@@ -1367,6 +1503,9 @@ std::atomic<int> g_autotune{0};
 constexpr size_t kTuneWsCap = (size_t)256 << 20;   // candidates whose split-K slabs exceed this are not tried
 constexpr size_t kTuneWinoCap = (size_t)768 << 20;  // same for the Winograd workspace (16 x (tiles x (C + K)) floats)
 
+// workspace of a split-K plan: one M x k slab of partial sums per split
+size_t splitk_ws_bytes(int splits, long M, int k) { return splits > 1 ? (size_t)splits * M * k * sizeof(float) : 0; }
+
 // The last slot carries the output stride AND whether the call has a residual operand (+ kKeyResidual): a call with a
 // residual cannot run as Winograd, so the two kinds of call of one shape are tuned and cached separately (a plan tuned for
 // one used to push the other onto the untuned analytic plan for good).
@@ -1384,10 +1523,17 @@ std::vector<Plan> tune_candidates(long M, int k, int ksteps, bool allow_split) {
       if (sp > 1 && (!allow_split || ksteps / sp < 2)) continue;
       const int sps = (ksteps + sp - 1) / sp;
       if ((ksteps + sps - 1) / sps != sp) continue;
-      if (sp > 1 && (size_t)sp * M * k * sizeof(float) > kTuneWsCap) continue;
+      if (splitk_ws_bytes(sp, M, k) > kTuneWsCap) continue;
       out.push_back(Plan{ci, sp, sps});
     }
   return out;
+}
+
+// room for every candidate the tuner may try on a shape (wino_bytes: its Winograd workspace, 0 if it has no such form)
+size_t tune_ws_bytes(long M, int k, int ksteps, size_t wino_bytes) {
+  size_t need = wino_bytes <= kTuneWinoCap ? wino_bytes : 0;
+  for (const Plan& cand : tune_candidates(M, k, ksteps, true)) need = std::max(need, splitk_ws_bytes(cand.splits, M, k));
+  return need;
 }
 
 bool lookup_plan(const ShapeKey& key, Plan* pl) {
@@ -1396,128 +1542,6 @@ bool lookup_plan(const ShapeKey& key, Plan* pl) {
   if (it == g_plan_cache.end()) return false;
   *pl = it->second;
   return true;
-}
-
-// ---- per-dispatch timing (frcnn_conv2d_profile_begin / _end) -----------------------------------------------------------
-// While a profile is open every kernel of frcnn_conv2d_fwd is launched through hipExtLaunchKernelGGL with its own
-// start / stop events: the pair brackets THAT dispatch on the launch stream (begin -> end of the kernel, the quantity
-// rocprofv3 --kernel-trace reports), without the event-packet overhead two separately recorded events add around a
-// launch.  bench.py's `roofline` is computed from these durations.
-struct ProfRec {
-  hipEvent_t e0, e1;
-  int call, kind;      // frcnn_conv2d_fwd call number since profile_begin; kind 0 = main kernel, 1 = split-K second pass
-};
-std::vector<ProfRec> g_prof;
-std::atomic<bool> g_prof_on{false};
-int g_prof_call = -1;
-
-bool prof_events(int kind, hipEvent_t* e0, hipEvent_t* e1, hipStream_t stream) {
-  if (!g_prof_on) return false;
-  // a capturing stream cannot take the timed launch form (events would become graph nodes): plain launch, no record
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return false;
-  if (hipEventCreate(e0) != hipSuccess) return false;
-  if (hipEventCreate(e1) != hipSuccess) { (void)hipEventDestroy(*e0); return false; }
-  g_prof.push_back(ProfRec{*e0, *e1, g_prof_call, kind});
-  return true;
-}
-
-template <int WM, int WN, int TM, int TN, bool ALIGNED, bool WINO = false>
-int launch_conv(const ConvParams& p, int splits, int groups, hipStream_t stream) {
-  constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-  constexpr size_t lds = (size_t)2 * (BM + BN) * LDS_PITCH * sizeof(float);
-  static std::atomic<bool> configured{false};   // idempotent attribute call: a race only repeats it
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f32<WM, WN, TM, TN, ALIGNED, WINO>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv: set LDS size: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, groups, splits);
-  hipEvent_t e0, e1;
-  if (prof_events(0, &e0, &e1, stream))
-    hipExtLaunchKernelGGL((conv_igemm_f32<WM, WN, TM, TN, ALIGNED, WINO>), grid, dim3(64 * WM * WN), (uint32_t)lds, stream, e0,
-                          e1, 0, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_f32<WM, WN, TM, TN, ALIGNED, WINO>), grid, dim3(64 * WM * WN), lds, stream, p);
-  return frcnn::check_launch("conv_igemm_f32");
-}
-
-template <int WM, int WN>
-int launch_conv_dma(const ConvParams& p, int splits, int groups, hipStream_t stream) {
-  constexpr int BM = 64 * WM, BN = 64 * WN;
-  constexpr size_t lds = (size_t)3 * (BM + BN) * 32 * sizeof(float);
-  static std::atomic<bool> configured{false};   // idempotent attribute call: a race only repeats it
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_dma_f32<WM, WN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv: set LDS size: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, groups, splits);
-  hipEvent_t e0, e1;
-  if (prof_events(0, &e0, &e1, stream))
-    hipExtLaunchKernelGGL((conv_igemm_dma_f32<WM, WN>), grid, dim3(512), (uint32_t)lds, stream, e0, e1, 0, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_dma_f32<WM, WN>), grid, dim3(512), lds, stream, p);
-  return frcnn::check_launch("conv_igemm_dma_f32");
-}
-
-template <int WM, int WN, int TM, int TN>
-int launch_conv_buf(const ConvParams& p, int splits, int groups, hipStream_t stream) {
-  constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-  constexpr size_t lds = (size_t)3 * (BM + BN) * 32 * sizeof(float);
-  static std::atomic<bool> configured{false};   // idempotent attribute call: a race only repeats it
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_buf_f32<WM, WN, TM, TN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv: set LDS size: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, groups, splits);
-  hipEvent_t e0, e1;
-  if (prof_events(0, &e0, &e1, stream))
-    hipExtLaunchKernelGGL((conv_igemm_buf_f32<WM, WN, TM, TN>), grid, dim3(64 * WM * WN), (uint32_t)lds, stream, e0, e1, 0, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_buf_f32<WM, WN, TM, TN>), grid, dim3(64 * WM * WN), lds, stream, p);
-  return frcnn::check_launch("conv_igemm_buf_f32");
-}
-
-int launch_conv_pbuf(const ConvParams& p, int splits, int groups, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)3 * (64 + 64) * 32 + (size_t)4 * 32 * LDS_PITCH) * sizeof(float);
-  static std::atomic<bool> configured{false};   // idempotent attribute call: a race only repeats it
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_pbuf_f32),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv: set LDS size: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  const long total = (long)p.tiles_m * p.tiles_n * groups * splits;
-  dim3 grid((unsigned)std::min<long>(total, 2L * NUM_CU));      // two resident workgroups per CU (66 KB of LDS each)
-  hipEvent_t e0, e1;
-  if (prof_events(0, &e0, &e1, stream))
-    hipExtLaunchKernelGGL(conv_igemm_pbuf_f32, grid, dim3(256), (uint32_t)lds, stream, e0, e1, 0, p, groups, splits);
-  else
-    hipLaunchKernelGGL(conv_igemm_pbuf_f32, grid, dim3(256), lds, stream, p, groups, splits);
-  return frcnn::check_launch("conv_igemm_pbuf_f32");
-}
-
-int launch_conv_dma2(const ConvParams& p, int splits, int groups, hipStream_t stream) {
-  constexpr size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
-  static std::atomic<bool> configured{false};   // idempotent attribute call: a race only repeats it
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_dma2_f32<2, 2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv: set LDS size: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, groups, splits);
-  hipEvent_t e0, e1;
-  if (prof_events(0, &e0, &e1, stream))
-    hipExtLaunchKernelGGL((conv_igemm_dma2_f32<2, 2>), grid, dim3(256), (uint32_t)lds, stream, e0, e1, 0, p);
-  else
-    hipLaunchKernelGGL((conv_igemm_dma2_f32<2, 2>), grid, dim3(256), lds, stream, p);
-  return frcnn::check_launch("conv_igemm_dma2_f32");
 }
 
 // tuning hook: 0 = register-staged kernels only, 1 = LDS-DMA kernel for the 8-wave tiles when C % 32 == 0
@@ -1532,9 +1556,12 @@ bool conv_args_ok(int n, int h, int w, int c, int k, int r, int s, int stride, i
 
 extern "C" int frcnn_conv2d_set_tile(int tm, int tn) {
   bool known = (tm == 0 && tn == 0);
-  for (int i = 0; i < kNumTiles; ++i) known = known || (kTiles[i].tm == tm && kTiles[i].tn == tn);
-  FRCNN_REQUIRE(known, "conv2d_set_tile: tiles are 64*tm x 64*tn with (tm,tn) in "
-                       "{(4,2),(2,4),(2,2),(2,1),(1,2),(1,1)} ((0,0) = automatic)");
+  std::string shapes;
+  for (int i = 0; i < kNumShapes; ++i) {
+    known = known || (kTiles[i].tm == tm && kTiles[i].tn == tn);
+    shapes += (i ? ",(" : "(") + std::to_string(kTiles[i].tm) + "," + std::to_string(kTiles[i].tn) + ")";
+  }
+  FRCNN_REQUIRE(known, "conv2d_set_tile: tiles are 64*tm x 64*tn with (tm,tn) in {%s} ((0,0) = automatic)", shapes.c_str());
   g_force_tm = tm;
   g_force_tn = tn;
   return FRCNN_OK;
@@ -1577,26 +1604,17 @@ extern "C" size_t frcnn_conv2d_fwd_ws_bytes(int n, int h, int w, int c, int k, i
       size_t need = 0;
       for (const Plan* pc : {h0 ? &c0 : nullptr, h1 ? &c1 : nullptr}) {
         if (!pc) continue;
-        need = std::max(need, pc->algo == 1 ? wino_bytes : (pc->splits > 1 ? (size_t)pc->splits * M * k * sizeof(float) : 0));
+        need = std::max(need, pc->algo == 1 ? wino_bytes : splitk_ws_bytes(pc->splits, M, k));
       }
       if (g_algo_mode == 2) need = std::max(need, wino_bytes);
       if (h0 && h1) return need;
       if (!g_autotune) return need;
-      size_t more = wino_bytes <= kTuneWinoCap ? wino_bytes : 0;
-      for (const Plan& cand : tune_candidates(M, k, ksteps, true))
-        if (cand.splits > 1) more = std::max(more, (size_t)cand.splits * M * k * sizeof(float));
-      return std::max(need, more);
+      return std::max(need, tune_ws_bytes(M, k, ksteps, wino_bytes));
     }
   }
-  if (split_k <= 0 && g_force_tm == 0 && g_autotune) {
-    size_t need = wino_bytes <= kTuneWinoCap ? wino_bytes : 0;   // not tuned yet: room for every candidate the tuner may try
-    for (const Plan& cand : tune_candidates(M, k, ksteps, true))
-      if (cand.splits > 1) need = std::max(need, (size_t)cand.splits * M * k * sizeof(float));
-    return need;
-  }
+  if (split_k <= 0 && g_force_tm == 0 && g_autotune) return tune_ws_bytes(M, k, ksteps, wino_bytes);   // not tuned yet
   if (g_algo_mode == 2 && split_k <= 0 && g_force_tm == 0 && wino) return wino_bytes;
-  const Plan pl = choose_plan((int)M, k, ksteps, split_k);
-  return pl.splits > 1 ? (size_t)pl.splits * M * k * sizeof(float) : 0;
+  return splitk_ws_bytes(choose_plan((int)M, k, ksteps, split_k).splits, M, k);
 }
 
 extern "C" int frcnn_conv2d_plan_algo(int n, int h, int w, int c, int k, int r, int s, int stride, int pad, int has_residual) {
@@ -1652,7 +1670,7 @@ extern "C" int frcnn_conv2d_import_plans(const int* in, int entries) {
     const int* row = in + e * 13;
     const int code = row[10] >> 4, cfg = row[10] & 15;
     const int algo = code >= 1 ? 1 : 0, fuse_in = code == 2 ? 1 : 0;
-    FRCNN_REQUIRE(row[10] >= 0 && cfg < kNumTiles && code <= 2 && (!fuse_in || (cfg == 5 && row[3] % BK == 0)) && row[11] >= 1 && row[11] <= 64 && row[12] >= 1 &&
+    FRCNN_REQUIRE(row[10] >= 0 && cfg < kNumTiles && code <= 2 && (!fuse_in || (cfg == kTile64x64 && row[3] % BK == 0)) && row[11] >= 1 && row[11] <= 64 && row[12] >= 1 &&
                       (algo == 0 || (row[11] == 1 && winograd_ok(row[5], row[6], row[7], row[8], row[3], row[4], row[9]))),   // a residual key (row[9] >= 256) fails winograd_ok: no Winograd plan for it
                   "conv2d_import_plans: entry %d is not a valid plan (tile %d, splits %d)", e, row[10], row[11]);
     if (algo == 1) continue;   // the Winograd GEMM derives its own K-steps (launch_winograd)
@@ -1847,7 +1865,7 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
   }
 }
 
-// launch one plan: main kernel + the split-K second pass (or the four launches of a Winograd plan)
+// launch the GEMM kernel of one plan: the tile's kernel for this C, staging mode and operand size (resolve_tile)
 int launch_gemm(ConvParams p, const Plan& pl, long M, int k, int groups, hipStream_t stream) {
   const TileCfg& tc = kTiles[pl.cfg];
   p.steps_per_split = pl.steps_per_split;
@@ -1855,87 +1873,17 @@ int launch_gemm(ConvParams p, const Plan& pl, long M, int k, int groups, hipStre
   p.tiles_m = (p.M + bm - 1) / bm;
   p.tiles_n = (k + bn - 1) / bn;
   const bool aligned = (p.C % BK) == 0;
-  int rc;
   if (pl.fuse_in) {
-    if (pl.cfg != 5 || !aligned) return frcnn::fail(FRCNN_ERR_ARG, "conv2d: fused Winograd input needs the 64x64 tile and C %% 32 == 0");
-    return launch_conv<2, 2, 1, 1, true, true>(p, 1, groups, stream);
+    if (pl.cfg != kTile64x64 || !aligned) return frcnn::fail(FRCNN_ERR_ARG, "conv2d: fused Winograd input needs the 64x64 tile and C %% 32 == 0");
+    return launch_reg<2, 2, 1, 1, true, true>(p, 1, groups, stream);
   }
-#define FRCNN_CONV_CASE(WM_, WN_, TM_, TN_)                                           \
-  rc = aligned ? launch_conv<WM_, WN_, TM_, TN_, true>(p, pl.splits, groups, stream) \
-               : launch_conv<WM_, WN_, TM_, TN_, false>(p, pl.splits, groups, stream)
-  switch (pl.cfg) {
-    case 0:
-      if (aligned && g_use_dma == 3 && p.xbytes && p.wbytes) rc = launch_conv_buf<4, 2, 2, 2>(p, pl.splits, groups, stream);
-      else if (aligned && g_use_dma) rc = launch_conv_dma<4, 2>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(4, 2, 2, 2);
-      break;
-    case 1:
-      if (aligned && g_use_dma == 3 && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 4, 2, 2>(p, pl.splits, groups, stream);
-      else if (aligned && g_use_dma) rc = launch_conv_dma<2, 4>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 4, 2, 2);
-      break;
-    case 2:
-      if (aligned && g_use_dma == 3 && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 2, 2>(p, pl.splits, groups, stream);
-      else if (aligned && g_use_dma == 2) rc = launch_conv_dma2(p, pl.splits, groups, stream);   // test hook, see set_staging
-      else FRCNN_CONV_CASE(2, 2, 2, 2);
-      break;
-    case 6:
-      if (aligned && g_use_dma) rc = launch_conv_dma2(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 2, 2);
-      break;
-    case 13:
-      if (aligned && g_use_dma && p.xbytes && p.wbytes) rc = launch_conv_pbuf(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 1, 1);
-      break;
-    case 10:
-      if (aligned && g_use_dma && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 2, 2>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 2, 2);
-      break;
-    case 11:
-      if (aligned && g_use_dma && p.xbytes && p.wbytes) rc = launch_conv_buf<4, 2, 2, 2>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(4, 2, 2, 2);
-      break;
-    case 12:
-      if (aligned && g_use_dma && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 4, 2, 2>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 4, 2, 2);
-      break;
-    case 3:
-      if (aligned && g_use_dma == 3 && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 2, 1>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 2, 1);
-      break;
-    case 4:
-      if (aligned && g_use_dma == 3 && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 1, 2>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 1, 2);
-      break;
-    case 7:
-      if (aligned && g_use_dma && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 1, 1>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 1, 1);
-      break;
-    case 8:
-      if (aligned && g_use_dma && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 2, 1>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 2, 1);
-      break;
-    case 9:
-      if (aligned && g_use_dma && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 1, 2>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 1, 2);
-      break;
-    default:
-      if (aligned && g_use_dma == 3 && p.xbytes && p.wbytes) rc = launch_conv_buf<2, 2, 1, 1>(p, pl.splits, groups, stream);
-      else FRCNN_CONV_CASE(2, 2, 1, 1);
-      break;
-  }
-#undef FRCNN_CONV_CASE
-  return rc;
+  return resolve_tile(pl.cfg, aligned, g_use_dma, p.xbytes && p.wbytes)(p, pl.splits, groups, stream);
 }
 
-// launches a 1-D grid kernel through the profiling events when a profile is open (kind 2 = Winograd transform)
-template <typename... Args, typename... Actual>
-int launch_1d(const char* what, void (*kernel)(Args...), size_t threads, hipStream_t stream, Actual... args) {
-  const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-  hipEvent_t e0, e1;
-  if (prof_events(2, &e0, &e1, stream)) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, e0, e1, 0, args...);
-  else hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
-  return frcnn::check_launch(what);
+// launches a 1-D grid kernel, one thread per element (profile kind 2 = Winograd transform)
+template <auto Kernel, typename... Args>
+int launch_1d(const char* what, size_t threads, hipStream_t stream, Args... args) {
+  return launch_kernel<Kernel>(what, 2, dim3((unsigned)((threads + 255) / 256)), 256, 0, stream, args...);
 }
 
 int launch_winograd(const ConvParams& p, const Plan& pl, const float* scale, const float* shift, float* y, int relu,
@@ -1948,10 +1896,10 @@ int launch_winograd(const ConvParams& p, const Plan& pl, const float* scale, con
   float* Mo = reinterpret_cast<float*>(base + g.m_off);
   int rc = FRCNN_OK;
   if (p.u_pre) U = const_cast<float*>(p.u_pre);   // read-only from here on
-  else rc = launch_1d("wino_filter_kernel", wino_filter_kernel, (size_t)p.K * (p.C / 4), stream, p.w, U, p.K, p.C / 4);
+  else rc = launch_1d<wino_filter_kernel>("wino_filter_kernel", (size_t)p.K * (p.C / 4), stream, p.w, U, p.K, p.C / 4);
   if (rc != FRCNN_OK) return rc;
   if (!pl.fuse_in)
-    rc = launch_1d("wino_input_kernel", wino_input_kernel, (size_t)g.T * (p.C / 4), stream, p.x, V, p.H, p.W, p.C / 4, g.th,
+    rc = launch_1d<wino_input_kernel>("wino_input_kernel", (size_t)g.T * (p.C / 4), stream, p.x, V, p.H, p.W, p.C / 4, g.th,
                    g.tw, g.T);
   if (rc != FRCNN_OK) return rc;
   // 16 GEMMs  Mo[xi] (T x K) = V[xi] (T x C) . U[xi]^T (K x C)  as ONE grouped 1x1 convolution over a 1 x T "image"
@@ -1983,7 +1931,7 @@ int launch_winograd(const ConvParams& p, const Plan& pl, const float* scale, con
   }
   rc = launch_gemm(q, gp, g.T, p.K, 16, stream);
   if (rc != FRCNN_OK) return rc;
-  return launch_1d("wino_output_kernel", wino_output_kernel, (size_t)g.T * (p.K / 4), stream, (const float*)Mo, scale, shift, y,
+  return launch_1d<wino_output_kernel>("wino_output_kernel", (size_t)g.T * (p.K / 4), stream, (const float*)Mo, scale, shift, y,
                    p.Ho, p.Wo, p.K / 4, g.th, g.tw, g.T, relu, p.mask, p.mscale);
 }
 
@@ -1996,21 +1944,15 @@ int launch_plan(ConvParams p, const Plan& pl, long M, int k, const float* scale,
   if (pl.splits > 1) {
     const size_t mk = (size_t)M * k;
     const int blocks = (int)std::min<size_t>((mk + 255) / 256, 2048);
-    hipEvent_t e0, e1;
-    if (prof_events(1, &e0, &e1, stream))
-      hipExtLaunchKernelGGL(conv_splitk_epilogue, dim3(blocks), dim3(256), 0, stream, e0, e1, 0,
-                            (const float*)p.partial, pl.splits, mk, k, scale, shift, residual, y, relu, p.mask, p.mscale);
-    else
-      hipLaunchKernelGGL(conv_splitk_epilogue, dim3(blocks), dim3(256), 0, stream, p.partial, pl.splits, mk, k,
-                         scale, shift, residual, y, relu, p.mask, p.mscale);
-    return frcnn::check_launch("conv_splitk_epilogue");
+    return launch_kernel<conv_splitk_epilogue>("conv_splitk_epilogue", 1, dim3(blocks), 256, 0, stream, (const float*)p.partial, pl.splits,
+                                               mk, k, scale, shift, residual, y, relu, p.mask, p.mscale);
   }
   return FRCNN_OK;
 }
 
 size_t plan_ws_bytes(const Plan& pl, const ConvParams& p, long M, int k) {
   if (pl.algo == 1) return wino_geom(p.M / (p.Ho * p.Wo), p.H, p.W, p.C, p.K).bytes;
-  return pl.splits > 1 ? (size_t)pl.splits * M * k * sizeof(float) : 0;
+  return splitk_ws_bytes(pl.splits, M, k);
 }
 
 // frcnn_conv2d_set_autotune(2): candidates are timed UNDER LOAD - kLoadCopies launches of the candidate in flight at once,
@@ -2058,7 +2000,7 @@ bool tune_plan(const ConvParams& p, long M, int k, const float* scale, const flo
       cands.push_back(pl);
     }
     if ((p.C % BK) == 0 && g_wino_fuse) {   // the 64x64 GEMM with the input transform in its A-tile load
-      Plan pl{5, 1, p.C / BK};
+      Plan pl{kTile64x64, 1, p.C / BK};
       pl.algo = 1;
       pl.fuse_in = 1;
       cands.push_back(pl);
@@ -2185,9 +2127,9 @@ int run_conv(const float* x, const float* wgt, const float* scale, const float* 
     pl = choose_plan(p.M, k, p.ksteps, allow_split ? split_k : 1);
     if (g_algo_mode == 2 && split_k <= 0 && g_force_tm == 0 && residual == nullptr &&
         winograd_ok(r, s, stride, pad, c, k, out_stride)) {
-      pl = Plan{M >= 2048 ? 2 : 5, 1, (c + BK - 1) / BK};   // forced Winograd without tuning: a mid-size GEMM tile
+      pl = Plan{M >= 2048 ? kTile128x128 : kTile64x64, 1, (c + BK - 1) / BK};   // forced Winograd without tuning: a mid-size GEMM tile
       pl.algo = 1;
-      if (g_wino_fuse == 2 && (c % BK) == 0) { pl.cfg = 5; pl.fuse_in = 1; }
+      if (g_wino_fuse == 2 && (c % BK) == 0) { pl.cfg = kTile64x64; pl.fuse_in = 1; }
     }
   }
   if (!have && split_k <= 0 && pl.splits > 1 && (!ws || ws_bytes < plan_ws_bytes(pl, p, M, k))) {

@@ -164,7 +164,10 @@ int frcnn_conv2d_clear_plans(void);
  * otherwise perturb the tuning; or shipped with a deployment: bench.py loads profiles/r05_plans.json).  Tile indices:
  * 0 256x128, 1 128x256 (8 waves, LDS-DMA three stages), 2 128x128, 3 128x64, 4 64x128, 5 64x64 (register-staged), 6 128x128
  * LDS-DMA two stages, 7 64x64, 8 128x64, 9 64x128, 10 128x128, 11 256x128, 12 128x256 (LDS-DMA through buffer loads, three
- * stages), 13 64x64 with PERSISTENT workgroups (one K-step stream across a workgroup's tiles).  export returns the number of cached entries (fills at most capacity_entries); import validates
+ * stages), 13 64x64 with PERSISTENT workgroups (one K-step stream across a workgroup's tiles).  An LDS-DMA index runs its
+ * kernel when C % 32 == 0 and frcnn_conv2d_set_staging is not 0 (7 .. 13: and both operands are below 2 GB); otherwise
+ * EVERY index, 11 and 12 included, runs the register-staged kernel of its tile shape.  The table these indices select
+ * from is kTiles in csrc/conv_igemm.hip.  export returns the number of cached entries (fills at most capacity_entries); import validates
  * every entry, then inserts all or none; an implicit-GEMM entry must split the ceil(r*s*c / 32) K-steps of its shape as
  * ceil(K-steps / steps per split) == splits. */
 int frcnn_conv2d_export_plans(int* out, int capacity_entries);
@@ -174,7 +177,8 @@ int frcnn_conv2d_import_plans(const int* in, int entries);
  * autotuner may pick the two-stage LDS-DMA 128x128 tile, plan tile index 6), 0 uses the register-staged kernels
  * everywhere, 2 additionally runs a FORCED 128x128 tile (frcnn_conv2d_set_tile(2, 2)) on the two-stage LDS-DMA kernel,
  * 3 runs FORCED tiles (and plan tile indices 0 .. 5) on the buffer-load LDS-DMA kernel (conv_igemm_buf_f32: plan tile
- * indices 7 .. 12 select it in every mode but 0; needs C % 32 == 0 and operands below 2 GB, else the register-staged kernel).
+ * indices 7 .. 12 select it in every mode but 0; needs C % 32 == 0 and operands below 2 GB, else the register-staged kernel
+ * - except that indices 0 / 1 in mode 3 with an operand of 2 GB or more stay on their mode-1 LDS-DMA kernel).
  * Results are bit-identical for split_k = 1. */
 int frcnn_conv2d_set_staging(int use_lds_dma);
 
