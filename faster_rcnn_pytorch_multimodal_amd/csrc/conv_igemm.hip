@@ -105,19 +105,14 @@ __device__ __forceinline__ void tile_coords(int tile, int tiles_m, int tiles_n, 
 // Epilogue shared by the conv kernels.  The MFMA operands are (weights, activations), so D has the PIXEL on the
 // lane (col = lane&31) and the CHANNEL in the registers: row = (r&3) + 8*(r>>2) + 4*(lane>>5).  Registers
 // 4g..4g+3 are four consecutive channels -> every access is a 16-byte vector per lane, and all residual loads of a
-// 32x32 tile are issued before its first store.
+// 32x32 tile are issued before its first store (res may alias nothing we write, but the compiler cannot know:
+// batching keeps 4 loads in flight instead of a load->wait->store chain per element).
 template <int TM, int TN>
 __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)[TM][TN], int m0, int n0, int wr, int wc,
                                               int lane, int gy = -1, int gz = -1) {
   if (gy < 0) gy = blockIdx.y;                     // (the persistent kernel walks groups / splits itself)
   if (gz < 0) gz = blockIdx.z;
   const size_t goff = (size_t)gy * p.gy;   // grouped launches have neither a residual nor split-K slabs
-  // The MFMA operands are (weights, activations), so D has the PIXEL on the lane (col = lane&31) and
-  // the CHANNEL in the registers: row = (r&3) + 8*(r>>2) + 4*(lane>>5).  Registers 4g..4g+3 are four
-  // consecutive channels -> every access of the epilogue is a 16-byte vector per lane, and all
-  // residual loads of a 32x32 tile are issued before its first store (res may alias nothing we
-  // write, but the compiler cannot know: batching keeps 4 loads in flight instead of a
-  // load->wait->store chain per element).
   const int mlane = lane & 31, nhalf = 4 * (lane >> 5);
   const bool vec = (p.K & 3) == 0;
   float* const slab = p.partial ? p.partial + (size_t)gz * p.M * p.K : nullptr;
@@ -265,6 +260,44 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, f32x16 (&
 // every load of a tile is issued unconditionally (and the compiler can count them: partial vmcnt waits)
 __device__ float g_zero_page[64];
 
+typedef __attribute__((address_space(3))) void* lds_ptr;
+typedef const __attribute__((address_space(1))) void* gbl_ptr;
+
+// The LDS image of the four LDS-DMA kernels: a stage is [BM + BN rows][32 floats], 128-byte rows WITHOUT padding, because a
+// DMA wave instruction writes lane l at base + 16 l, i.e. 8 whole rows (lane l -> 16-byte slot l & 7 of row l >> 3).  Bank
+// conflicts of the ds_read_b128 fragment reads (lane -> row) are removed by an XOR swizzle: logical chunk c of a row lives in
+// slot swizzled_chunk(row, c).  The XOR is its own inverse: the DMA side applies the same function to its slot on the per-lane
+// SOURCE address, the fragment reads to the LDS address (guide rule 21).
+__device__ __forceinline__ int swizzle_key(int row) { return (row >> 1) & 7; }
+__device__ __forceinline__ int swizzled_chunk(int row, int chunk) { return chunk ^ swizzle_key(row); }
+
+// Workgroup `block` of the tile grid -> first pixel m0 and first channel n0 of its BM x BN tile (XCD remap, column-group raster)
+template <int BM, int BN>
+__device__ __forceinline__ void tile_origin(const ConvParams& p, int block, int& m0, int& n0) {
+  int tile_m, tile_n;
+  tile_coords(xcd_remap(block, p.tiles_m * p.tiles_n), p.tiles_m, p.tiles_n, tile_m, tile_n);
+  m0 = tile_m * BM;
+  n0 = tile_n * BN;
+}
+
+// K-split z reduces the K-steps [begin, begin + returned count); the count is <= 0 for a split past the end
+__device__ __forceinline__ int split_range(const ConvParams& p, int z, int& begin) {
+  begin = z * p.steps_per_split;
+  return min(begin + p.steps_per_split, p.ksteps) - begin;
+}
+
+// One group of k = 8: 4 x TM x TN MFMAs.  Operands are (weights, activations): D col (lane) = pixel, D row (register) = channel
+template <int TM, int TN>
+__device__ __forceinline__ void mma_step(f32x16 (&acc)[TM][TN], const f32x4* fa, const f32x4* fb) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[j][q], fa[i][q], acc[i][j], 0, 0, 0);
+}
+
 // (the one-accumulator wave of the 64x64 tile is held to 128 VGPRs: four workgroups per CU, as its 36 KB of LDS allow)
 template <int WM, int WN, int TM, int TN, bool ALIGNED, bool WINO = false>
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_f32(const ConvParams p) {
@@ -284,13 +317,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_f32(const ConvPara
   const float* const px = p.x + (size_t)blockIdx.y * p.gx;
   const float* const pw = p.w + (size_t)blockIdx.y * p.gw;
 
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int tile = xcd_remap(blockIdx.x, ntiles);
-  int tile_m, tile_n;
-  tile_coords(tile, p.tiles_m, p.tiles_n, tile_m, tile_n);
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
 
-  const int step_begin = blockIdx.z * p.steps_per_split;
+  const int step_begin = blockIdx.z * p.steps_per_split;   // (split_range written out: nsteps is formed below, where it is used)
   const int step_end = min(step_begin + p.steps_per_split, p.ksteps);
 
   // ---- per-thread staging geometry: thread t moves chunk kc of rows (t>>3) + RPP*i ---------------
@@ -440,16 +470,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_f32(const ConvPara
 #pragma unroll
     for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f32x4*>(Bb + j * 32 * LDS_PITCH);
   };
-  // operands are (weights, activations): D col (lane) = pixel, D row (register) = channel
-  auto mma = [&](const f32x4* fa, const f32x4* fb) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[j][q], fa[i][q], acc[i][j], 0, 0, 0);
-  };
+  auto mma = [&](const f32x4* fa, const f32x4* fb) { mma_step(acc, fa, fb); };
 
   const int nsteps = step_end - step_begin;
   if (nsteps > 0) {
@@ -500,11 +521,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_f32(const ConvPara
 // LDS-DMA variant for the 8-wave tiles (C % 32 == 0): the A/B tiles go global -> LDS with
 // global_load_lds_dwordx4 (no VGPR staging, no ds_write pass), three LDS stages, loads issued two K-steps
 // ahead, ONE raw s_barrier per K-step behind a counted vmcnt.
-//   LDS stage = [BM + BN rows][32 floats], 128-byte rows WITHOUT padding: an LDS-DMA wave instruction writes
-//   lane i at base + 16*i, i.e. 8 whole rows per instruction.  Bank conflicts of the ds_read_b128 fragment
-//   reads (lane -> row) are removed by an XOR swizzle of the 16-byte chunk index with (row >> 1) & 7, applied
-//   on the per-lane GLOBAL source address and again on the read address (guide rule 21).
-//   Out-of-range lanes (padding taps, M / K tails) read a zero page instead of branching.
+//   LDS image and swizzle: see swizzled_chunk.  Out-of-range lanes (padding taps, M / K tails) read a zero page instead
+//   of branching.
 // Numerics are those of conv_igemm_f32 (same k order), so split_k == 1 results are bit-identical.
 // ------------------------------------------------------------------------------------------------
 
@@ -522,14 +540,9 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
   const int wr = wave / WN, wc = wave % WN;
   const float* const px = p.x + (size_t)blockIdx.y * p.gx;
   const float* const pw = p.w + (size_t)blockIdx.y * p.gw;
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int tile = xcd_remap(blockIdx.x, ntiles);
-  int tile_m, tile_n;
-  tile_coords(tile, p.tiles_m, p.tiles_n, tile_m, tile_n);
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int step_begin = blockIdx.z * p.steps_per_split;
-  const int step_end = min(step_begin + p.steps_per_split, p.ksteps);
-  const int nsteps = step_end - step_begin;
+  int m0, n0, step_begin;
+  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+  const int nsteps = split_range(p, blockIdx.z, step_begin);
 
   // ---- per-lane sources: lane i of instruction q feeds row 8q + (i >> 3), physical chunk i & 7 -------------
   const int lrow = lane >> 3, lchunk = lane & 7;
@@ -538,7 +551,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
   for (int j = 0; j < PA; ++j) {
     const int row = (wave * PA + j) * 8 + lrow;
     const int m = m0 + row;
-    a_swz[j] = (lchunk ^ ((row >> 1) & 7)) * 4;
+    a_swz[j] = swizzled_chunk(row, lchunk) * 4;
     if (m < p.M) {
       const int img = m / (p.Ho * p.Wo);
       const int rem = m - img * p.Ho * p.Wo;
@@ -557,7 +570,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
   for (int j = 0; j < PB; ++j) {
     const int row = (wave * PB + j) * 8 + lrow;
     const int n = n0 + row;
-    b_src[j] = n < p.K ? pw + (size_t)n * p.Ktot + (lchunk ^ ((row >> 1) & 7)) * 4 : nullptr;
+    b_src[j] = n < p.K ? pw + (size_t)n * p.Ktot + swizzled_chunk(row, lchunk) * 4 : nullptr;
   }
   int tr, ts, tc;
   {
@@ -567,8 +580,6 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
     tr = tap / p.S;
     ts = tap - tr * p.S;
   }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr;
   // issue() is called for consecutive steps (the tap state advances by one step per call)
   auto issue = [&](int step, int stage) {
     float* sA = smem + stage * STAGE + (wave * PA) * 8 * 32;
@@ -607,13 +618,13 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
   for (int i = 0; i < TM; ++i) {
     const int row = (wr * TM + i) * 32 + (lane & 31);
     fa_row[i] = row * 32;
-    fa_x[i] = (row >> 1) & 7;
+    fa_x[i] = swizzle_key(row);
   }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int row = (wc * TN + j) * 32 + (lane & 31);
     fb_row[j] = BM * 32 + row * 32;
-    fb_x[j] = (row >> 1) & 7;
+    fb_x[j] = swizzle_key(row);
   }
   const int lh = lane >> 5;
   f32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
@@ -699,14 +710,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
   const int wr = wave / WN, wc = wave % WN;
   const float* const px = p.x + (size_t)blockIdx.y * p.gx;
   const float* const pw = p.w + (size_t)blockIdx.y * p.gw;
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int tile = xcd_remap(blockIdx.x, ntiles);
-  int tile_m, tile_n;
-  tile_coords(tile, p.tiles_m, p.tiles_n, tile_m, tile_n);
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int step_begin = blockIdx.z * p.steps_per_split;
-  const int step_end = min(step_begin + p.steps_per_split, p.ksteps);
-  const int nsteps = step_end - step_begin;
+  int m0, n0, step_begin;
+  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+  const int nsteps = split_range(p, blockIdx.z, step_begin);
 
   // ---- per-lane sources: lane i of instruction q feeds row 8q + (i >> 3), physical chunk i & 7 -------------
   const int lrow = lane >> 3, lchunk = lane & 7;
@@ -715,7 +721,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
   for (int j = 0; j < PA; ++j) {
     const int row = (wave * PA + j) * 8 + lrow;
     const int m = m0 + row;
-    a_swz[j] = (lchunk ^ ((row >> 1) & 7)) * 4;
+    a_swz[j] = swizzled_chunk(row, lchunk) * 4;
     if (m < p.M) {
       const int img = m / (p.Ho * p.Wo);
       const int rem = m - img * p.Ho * p.Wo;
@@ -734,7 +740,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
   for (int j = 0; j < PB; ++j) {
     const int row = (wave * PB + j) * 8 + lrow;
     const int n = n0 + row;
-    b_src[j] = n < p.K ? pw + (size_t)n * p.Ktot + (lchunk ^ ((row >> 1) & 7)) * 4 : nullptr;
+    b_src[j] = n < p.K ? pw + (size_t)n * p.Ktot + swizzled_chunk(row, lchunk) * 4 : nullptr;
   }
   int tr, ts, tc;
   {
@@ -744,8 +750,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
     tr = tap / p.S;
     ts = tap - tr * p.S;
   }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr;
   // issue() is called for consecutive steps (the tap state advances by one step per call)
   auto issue = [&](int step, int stage) {
     float* sA = smem + stage * STAGE + (wave * PA) * 8 * 32;
@@ -784,13 +788,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
   for (int i = 0; i < TM; ++i) {
     const int row = (wr * TM + i) * 32 + (lane & 31);
     fa_row[i] = row * 32;
-    fa_x[i] = (row >> 1) & 7;
+    fa_x[i] = swizzle_key(row);
   }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int row = (wc * TN + j) * 32 + (lane & 31);
     fb_row[j] = BM * 32 + row * 32;
-    fb_x[j] = (row >> 1) & 7;
+    fb_x[j] = swizzle_key(row);
   }
   const int lh = lane >> 5;
   f32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
@@ -884,14 +888,9 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
   const int wr = wave / WN, wc = wave % WN;
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int tile = xcd_remap(blockIdx.x, ntiles);
-  int tile_m, tile_n;
-  tile_coords(tile, p.tiles_m, p.tiles_n, tile_m, tile_n);
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int step_begin = blockIdx.z * p.steps_per_split;
-  const int step_end = min(step_begin + p.steps_per_split, p.ksteps);
-  const int nsteps = step_end - step_begin;
+  int m0, n0, step_begin;
+  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+  const int nsteps = split_range(p, blockIdx.z, step_begin);
 
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.x + (size_t)blockIdx.y * p.gx), 0, (int)p.xbytes, 0x00020000);
@@ -906,7 +905,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
   for (int j = 0; j < PA; ++j) {
     const int row = (wave * PA + j) * 8 + lrow;
     const int m = m0 + row;
-    a_swz[j] = (unsigned)((lchunk ^ ((row >> 1) & 7)) * 16);
+    a_swz[j] = (unsigned)(swizzled_chunk(row, lchunk) * 16);
     if (m < p.M) {
       const int img = m / (p.Ho * p.Wo);
       const int rem = m - img * p.Ho * p.Wo;
@@ -925,7 +924,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
   for (int j = 0; j < PB; ++j) {
     const int row = (wave * PB + j) * 8 + lrow;
     const int n = n0 + row;
-    vB[j] = n < p.K ? (unsigned)(n * p.Ktot * 4 + (lchunk ^ ((row >> 1) & 7)) * 16) : OOB;
+    vB[j] = n < p.K ? (unsigned)(n * p.Ktot * 4 + swizzled_chunk(row, lchunk) * 16) : OOB;
   }
   int tr, ts, tc;
   {
@@ -936,7 +935,6 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
     ts = tap - tr * p.S;
   }
   bool new_tap = true;
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   // issue() is called for consecutive steps (the tap state advances by one step per call)
   auto issue = [&](int step, int stage) {
     float* sA = smem + stage * STAGE + (wave * PA) * 8 * 32;
@@ -979,13 +977,13 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
   for (int i = 0; i < TM; ++i) {
     const int row = (wr * TM + i) * 32 + (lane & 31);
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) fa_off[i][kk] = row * 32 + (((2 * kk + lh) ^ ((row >> 1) & 7)) << 2);
+    for (int kk = 0; kk < 4; ++kk) fa_off[i][kk] = row * 32 + (swizzled_chunk(row, 2 * kk + lh) << 2);
   }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int row = (wc * TN + j) * 32 + (lane & 31);
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) fb_off[j][kk] = BM * 32 + row * 32 + (((2 * kk + lh) ^ ((row >> 1) & 7)) << 2);
+    for (int kk = 0; kk < 4; ++kk) fb_off[j][kk] = BM * 32 + row * 32 + (swizzled_chunk(row, 2 * kk + lh) << 2);
   }
   f32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
   auto read_frags = [&](f32x4* fa, f32x4* fb, int stage, int kk) {
@@ -995,15 +993,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
 #pragma unroll
     for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f32x4*>(base + fb_off[j][kk]);
   };
-  auto mma = [&](const f32x4* fa, const f32x4* fb) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[j][q], fa[i][q], acc[i][j], 0, 0, 0);
-  };
+  auto mma = [&](const f32x4* fa, const f32x4* fb) { mma_step(acc, fa, fb); };
 
   // Schedule of one K-step as in conv_igemm_dma_f32: the barrier sits in the MIDDLE of the step (stage s+1 has landed for
   // every wave and every wave is past step s-1), the loads of step s+2 are issued right behind it.
@@ -1072,21 +1062,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
   const int ntiles = p.tiles_m * p.tiles_n;
   const int total = ntiles * groups * splits;
   const int stride = gridDim.x;
-  typedef __attribute__((address_space(3))) void* lds_ptr;
 
   // item -> (tile, group, split); tiles in the XCD-aware raster order of the other kernels
   auto item_coords = [&](int item, int& m0, int& n0, int& g, int& z) {
     const int tl = item % ntiles, gz = item / ntiles;
     g = gz % groups;
     z = gz / groups;
-    int tile_m, tile_n;
-    tile_coords(xcd_remap(tl, ntiles), p.tiles_m, p.tiles_n, tile_m, tile_n);
-    m0 = tile_m * BM;
-    n0 = tile_n * BN;
-  };
-  auto item_steps = [&](int z, int& begin) {
-    begin = z * p.steps_per_split;
-    return min(begin + p.steps_per_split, p.ksteps) - begin;
+    tile_origin<BM, BN>(p, tl, m0, n0);
   };
 
   // ---- producer cursor: the item / step whose tiles are issued next ------------------------------------------------------
@@ -1101,7 +1083,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
   auto producer_setup = [&]() {                        // geometry of item p_item (uniform: p_item < total)
     int m0, n0, g, z;
     item_coords(p_item, m0, n0, g, z);
-    p_nst = item_steps(z, p_begin);
+    p_nst = split_range(p, z, p_begin);
     p_step = 0;
     rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (size_t)g * p.gx), 0, (int)p.xbytes, 0x00020000);
     rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w + (size_t)g * p.gw), 0, (int)p.wbytes, 0x00020000);
@@ -1109,7 +1091,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
     for (int j = 0; j < PA; ++j) {
       const int row = (wave * PA + j) * 8 + lrow;
       const int m = m0 + row;
-      a_swz[j] = (unsigned)((lchunk ^ ((row >> 1) & 7)) * 16);
+      a_swz[j] = (unsigned)(swizzled_chunk(row, lchunk) * 16);
       if (m < p.M) {
         const int img = m / (p.Ho * p.Wo);
         const int rem = m - img * p.Ho * p.Wo;
@@ -1128,7 +1110,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
     for (int j = 0; j < PB; ++j) {
       const int row = (wave * PB + j) * 8 + lrow;
       const int n = n0 + row;
-      vB[j] = n < p.K ? (unsigned)(n * p.Ktot * 4 + (lchunk ^ ((row >> 1) & 7)) * 16) : OOB;
+      vB[j] = n < p.K ? (unsigned)(n * p.Ktot * 4 + swizzled_chunk(row, lchunk) * 16) : OOB;
     }
     const int kf = p_begin * BK;
     const int tap = kf / p.C;
@@ -1174,7 +1156,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
   const int lh = lane >> 5;
-  int fa_off[4], fb_off[4];
+  int fa_off[4], fb_off[4];   // (must match swizzle_key / swizzled_chunk; spelled out here: through the function this kernel takes 116 VGPRs, not 114)
   {
     const int rowa = wr * 32 + (lane & 31), rowb = wc * 32 + (lane & 31);
 #pragma unroll
@@ -1189,10 +1171,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
     fa = *reinterpret_cast<const f32x4*>(base + fa_off[kk]);
     fb = *reinterpret_cast<const f32x4*>(base + fb_off[kk]);
   };
-  auto mma = [&](const f32x4& fa, const f32x4& fb) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[q], fa[q], acc[0][0], 0, 0, 0);
-  };
+  auto mma = [&](const f32x4& fa, const f32x4& fb) { mma_step(acc, &fa, &fb); };
 
   if (blockIdx.x >= total) return;                     // (uniform) more workgroups than items: nothing to do
   // The stream: step g of this workgroup's items lives in stage g % 3.  `ahead` = steps issued - steps consumed (1 or 2 at the
@@ -1209,7 +1188,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
   for (int item = blockIdx.x; item < total; item += stride) {
     int m0, n0, g, z, begin;
     item_coords(item, m0, n0, g, z);
-    const int nst = item_steps(z, begin);
+    const int nst = split_range(p, z, begin);
     for (int s = 0; s < nst; ++s) {
       const int next = stage == 2 ? 0 : stage + 1;
       const bool more = ahead >= 2;
