@@ -20,6 +20,9 @@ A graph is specific to (H, W, C, capacity of the gt buffer); ``Network.train_ste
 ``net.enable_train_graphs()`` was called and falls back to the eager step for what a graph cannot express (``graphable``:
 BatchNorm with momentum=None, more don't-care boxes than the buffer holds).
 """
+import contextlib
+import warnings
+
 import numpy as np
 import torch
 
@@ -77,6 +80,33 @@ def inline_graphs_supported():
 
 class InlineCaptureUnsafe(RuntimeError):
     """An in-line (single-chain) capture holds node kinds the packet-captured replay path is known to mishandle."""
+
+
+class ReplayMismatch(RuntimeError):
+    """The replays of a single-chain captured step do not reproduce each other's gradients (``check_replays``)."""
+
+
+@contextlib.contextmanager
+def leaves_no_trace(net, grads, bn_modules):
+    """The passes run inside are not training steps (warm-up and capture on a placeholder frame, the replay check): on
+    exit, also when the body raises, ``grads``, the modules' running statistics and ``num_batches_tracked`` and the net's
+    uncertainty-draw counter ``_uc_calls`` hold what they held on entry.  Copies run on the current stream."""
+    held = [g.clone() for g in grads]
+    stats = [(m, m.running_mean.clone(), m.running_var.clone(),
+              m.num_batches_tracked.clone() if m.num_batches_tracked is not None else None) for m in bn_modules]
+    uc_calls = getattr(net, '_uc_calls', 0)
+    try:
+        yield
+    finally:
+        with torch.no_grad():
+            for g, h in zip(grads, held):
+                g.copy_(h)
+            for m, mean, var, nbt in stats:
+                m.running_mean.copy_(mean)
+                m.running_var.copy_(var)
+                if nbt is not None:
+                    m.num_batches_tracked.copy_(nbt)
+        net._uc_calls = uc_calls
 
 
 _NODE_KINDS = {0: 'kernel', 1: 'memcpy', 2: 'memset', 3: 'host', 4: 'graph', 5: 'empty', 6: 'wait_event', 7: 'event_record',
@@ -197,63 +227,50 @@ class TrainStepRunner:
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
         own = [p.grad for p in params]
-        if grads is not None:                       # warm-up and capture see the slot's buffers as the gradients
-            for p, g in zip(params, grads):
-                p.grad = g
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        saved = [p.grad.clone() for p in net.parameters() if p.requires_grad]
-        # the warm-up / capture steps run BatchNorm on batch statistics of a zero frame: keep the running statistics
-        stats = [(m, m.running_mean.clone(), m.running_var.clone(),
-                  m.num_batches_tracked.clone() if m.num_batches_tracked is not None else None) for m in self.bn_modules]
-        with torch.cuda.stream(side):
-            ops.set_conv_autotune(autotune)
-            try:
-                for _ in range(max(warmup, 1)):
-                    self._step()
-            finally:
-                torch.cuda.synchronize(dev)
-                ops.set_conv_autotune(False)
-            self._step()              # once more with the tuned plans: allocator and caches warm
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        # Filter gradients are accumulated into param.grad by this package's own launches on the side stream
-        # (autograd_ops._wgrad), never by autograd's AccumulateGrad nodes: those run on the stream the parameter was
-        # created on (the default stream, outside the capture) and were measured to race with the captured backward
-        # (up to 1 % gradient error); the side-stream form is exact and lets the filter gradients overlap the chain.
-        self.graph = torch.cuda.CUDAGraph(keep_graph=True)
-        prev = (autograd_ops.ASYNC_WGRAD, autograd_ops.WGRAD_ON_SIDE_STREAM, autograd_ops.GROUP_WGRAD)
-        autograd_ops.ASYNC_WGRAD = True
-        autograd_ops.WGRAD_ON_SIDE_STREAM = not inline
-        # The grouped filter gradients of a stage (autograd_ops.GROUP_WGRAD: the 22 equal Bottlenecks of layer3 in one unsplit
-        # launch).  In line they cost nothing in overlap - there is no side chain to trail.  On the side stream they used to lose
-        # (they start when their stage's backward is over); with the LDS-DMA kernel that adds into param.grad itself they win:
-        # 14.7 -> 14.3 ms per captured FPN step (round 5, same-box A/B; groups of 8: 14.3, of 4: 14.6)
-        autograd_ops.GROUP_WGRAD = True if group_wgrad is None else bool(group_wgrad)
-        if debug_dump:
-            self.graph.enable_debug_mode()
+        # Filter gradients are accumulated into param.grad by this package's own launches (autograd_ops._wgrad), never by
+        # autograd's AccumulateGrad nodes: those run on the stream the parameter was created on (the default stream, outside
+        # the capture) and were measured to race with the captured backward (up to 1 % gradient error).
+        # Grouped per stage (the 22 equal Bottlenecks of layer3 in one unsplit launch): in line that costs nothing in overlap -
+        # there is no side chain to trail.  On the side stream the groups used to lose (they start when their stage's backward
+        # is over); with the LDS-DMA kernel that adds into param.grad itself they win: 14.7 -> 14.3 ms per captured FPN step
+        # (round 5, same-box A/B; groups of 8: 14.3, of 4: 14.6)
+        schedule = autograd_ops.WgradSchedule(accumulate=True, side_stream=not inline,
+                                              grouped=True if group_wgrad is None else bool(group_wgrad),
+                                              bn_stat_sink=self.bn_private)
         self.inline = bool(inline)
-        autograd_ops.BN_STAT_SINK = self.bn_private
+        side = torch.cuda.Stream(device=dev)
         try:
-            with capture(self.graph):
-                self.loss, self.counts = self._step()
+            if grads is not None:                   # warm-up and capture see the slot's buffers as the gradients
+                for p, g in zip(params, grads):
+                    p.grad = g
+            # both run on a placeholder frame (BatchNorm on batch statistics of a zero frame): they leave no trace
+            with leaves_no_trace(net, [p.grad for p in params], self.bn_modules):
+                side.wait_stream(torch.cuda.current_stream(dev))
+                try:
+                    # The warm-up passes run under the eager schedule, not the one the capture bakes in.
+                    with torch.cuda.stream(side):
+                        ops.set_conv_autotune(autotune)
+                        try:
+                            for _ in range(max(warmup, 1)):
+                                self._step()
+                        finally:
+                            torch.cuda.synchronize(dev)
+                            ops.set_conv_autotune(False)
+                        self._step()              # once more with the tuned plans: allocator and caches warm
+                finally:
+                    torch.cuda.current_stream(dev).wait_stream(side)
+                    torch.cuda.synchronize(dev)
+                self.graph = torch.cuda.CUDAGraph(keep_graph=True)
+                if debug_dump:
+                    self.graph.enable_debug_mode()
+                with autograd_ops.wgrad_schedule(schedule), capture(self.graph):
+                    self.loss, self.counts = self._step()
+                if debug_dump:
+                    self.graph.debug_dump(debug_dump)
+                self.node_kinds, self.nodes, self.edges = graph_node_kinds(self.graph)
         finally:
-            autograd_ops.ASYNC_WGRAD, autograd_ops.WGRAD_ON_SIDE_STREAM, autograd_ops.GROUP_WGRAD = prev
-            autograd_ops.BN_STAT_SINK = None
-        if debug_dump:
-            self.graph.debug_dump(debug_dump)
-        self.node_kinds, self.nodes, self.edges = graph_node_kinds(self.graph)
-        # the warm-up and capture passes ran on a placeholder frame: drop what they added to the gradients and statistics
-        with torch.no_grad():
-            for p, g in zip(params, saved):
-                p.grad.copy_(g)
-            for m, mean, var, nbt in stats:
-                m.running_mean.copy_(mean)
-                m.running_var.copy_(var)
-                if nbt is not None:
-                    m.num_batches_tracked.copy_(nbt)
-        for p, g in zip(params, own):
-            p.grad = g
+            for p, g in zip(params, own):
+                p.grad = g
         if self.inline and self.node_kinds.get('memset', 0) and not packet_capture_disabled():
             raise InlineCaptureUnsafe("single-chain capture of the training step holds %d memset nodes (kinds %s): the runtime's "
                                       "packet-captured replay is not trusted with them" % (self.node_kinds['memset'], self.node_kinds))
@@ -374,14 +391,12 @@ def after_optimizer_step(net):
 def check_replays(net, runner, blobs, grads):
     """A single-chain graph must give the same gradients on every replay (the runtime fault described at
     ``inline_graphs_supported`` shows from the second replay on): replay the first captured step three times on this
-    frame with the same sampling seeds and compare the increments.  Raises instead of training on wrong gradients."""
+    frame with the same sampling seeds and compare the increments.  Raises ``ReplayMismatch`` instead of training on
+    wrong gradients; the check does not count as three training steps (``leaves_no_trace``)."""
     torch.cuda.synchronize(torch.device(net._device))
-    held = [g.clone() for g in grads]
-    stats = [(m, m.running_mean.clone(), m.running_var.clone(),
-              m.num_batches_tracked.clone() if m.num_batches_tracked is not None else None) for m in runner.bn_modules]
-    uc_calls = getattr(net, '_uc_calls', 0)
     incs = []
-    with torch.no_grad():
+    with leaves_no_trace(net, grads, runner.bn_modules), torch.no_grad():
+        uc_calls = getattr(net, '_uc_calls', 0)
         for _ in range(3):
             torch._foreach_zero_(grads)
             state = torch.random.get_rng_state()
@@ -390,14 +405,6 @@ def check_replays(net, runner, blobs, grads):
             torch.random.set_rng_state(state)               # ... and the same two sampling seeds for every replay
             torch.cuda.synchronize(torch.device(net._device))
             incs.append([g.clone() for g in grads])
-        for g, h in zip(grads, held):
-            g.copy_(h)
-        net._uc_calls = uc_calls
-        for m, mean, var, nbt in stats:                     # the check must not count as three training steps
-            m.running_mean.copy_(mean)
-            m.running_var.copy_(var)
-            if nbt is not None:
-                m.num_batches_tracked.copy_(nbt)
     # per tensor, relative to that tensor's own largest increment (a corrupted small-magnitude gradient must not hide
     # behind the largest one); tensors whose increment is below 1e-6 of the global scale are compared on that floor
     top = max(float(a.abs().max()) for a in incs[0]) or 1.0
@@ -408,26 +415,37 @@ def check_replays(net, runner, blobs, grads):
         if not dev <= worst:          # NaN counts as the worst
             worst, worst_i = dev, i
     if not worst <= 1e-3:
-        raise RuntimeError("a replayed single-chain training graph does not reproduce its own gradients "
-                           "(gradient tensor %d deviates by %.3e of its own scale; node kinds %s)."
-                           % (worst_i, worst, runner.node_kinds))
+        raise ReplayMismatch("a replayed single-chain training graph does not reproduce its own gradients "
+                             "(gradient tensor %d deviates by %.3e of its own scale; node kinds %s)."
+                             % (worst_i, worst, runner.node_kinds))
+
+
+def capture_with_fallback(net, blobs, inline, height, width, channels, num_gt, info, grads=None, autotune=True,
+                          defer_bn_stats=False):
+    """The captured step of this frame's shape; ``runner.inline`` says in which form.  ``inline``: ONE chain with the filter
+    gradients in line when the chain replays faithfully (no memset node, three replays reproduce each other:
+    ``check_replays`` on ``blobs``), else - with a warning - the forked form with the filter gradients on a side stream.
+    Only those two findings choose the forked capture: any other error of the capture or the check propagates."""
+    def runner(inline, autotune):
+        return TrainStepRunner(net, height, width, channels, num_gt, info, autotune=autotune, grads=grads, inline=inline,
+                               defer_bn_stats=defer_bn_stats)
+    if inline:
+        try:
+            chain = runner(True, autotune)
+            check_replays(net, chain, blobs, grads if grads is not None else [p.grad for p in net.parameters() if p.requires_grad])
+            return chain
+        except (InlineCaptureUnsafe, ReplayMismatch) as e:
+            warnings.warn("%s; capturing the forked graph (filter gradients on a side stream: correct, but replays on "
+                          "different streams do not overlap) instead" % e)
+            autotune = False
+    return runner(False, autotune)
 
 
 def captured_step(net, height, width, channels, num_gt, info, blobs):
-    """The runner behind ``Network.train_step`` (one captured step at a time): ONE chain of kernel nodes with the filter
-    gradients in line and grouped per stage when the chain replays faithfully (no memset node, three replays reproduce each
-    other: ``check_replays``), else the forked form with the filter gradients on a side stream.  Measured (round 5): the
-    forked graph's side branch buys nothing on this runtime - 14.2 ms per FPN step against 13.75 ms for the single chain."""
-    import warnings
-    if inline_graphs_supported():
-        try:
-            runner = TrainStepRunner(net, height, width, channels, num_gt, info, inline=True)
-            check_replays(net, runner, blobs, [p.grad for p in net.parameters() if p.requires_grad])
-            return runner
-        except (InlineCaptureUnsafe, RuntimeError) as e:
-            warnings.warn("train_step: %s; capturing the forked graph (filter gradients on a side stream) instead" % e)
-            return TrainStepRunner(net, height, width, channels, num_gt, info, autotune=False, inline=False)
-    return TrainStepRunner(net, height, width, channels, num_gt, info, inline=False)
+    """The runner behind ``Network.train_step`` (one captured step at a time): the single chain, grouped per stage, when
+    ``capture_with_fallback`` accepts it.  Measured (round 5): the forked graph's side branch buys nothing on this runtime -
+    14.2 ms per FPN step against 13.75 ms for the single chain."""
+    return capture_with_fallback(net, blobs, inline_graphs_supported(), height, width, channels, num_gt, info)
 
 
 class TrainPipeline:
@@ -443,7 +461,7 @@ class TrainPipeline:
     MEASURED: forked graphs (filter gradients on a side stream) of different slots do not overlap - 2 / 4 frames in flight ran
     at 16.7 / 17.1 ms per res101+FPN 1000x600 step against 17.0 ms for one (profiles/r03_train_step.md); single-chain graphs
     (``inline``) do: 10.3 ms per step with 3 in flight against 14.7 ms one at a time (profiles/r04_bench.json).
-    cfg.TRAIN.FRAMES_IN_FLIGHT (default 3) is the solver's slot count.
+    cfg.TRAIN.FRAMES_IN_FLIGHT (default 4) is the solver's slot count.
     BatchNorm on batch statistics (LiDAR backbone, FIXED_BLOCKS == -1): the slots' captured launches write their frame's
     batch statistics to slot-private buffers and ``submit`` folds them into the modules' running statistics in SUBMISSION
     order (``TrainStepRunner.fold_bn_stats`` chained by an event from frame to frame) - concurrent in-kernel updates of
@@ -454,7 +472,6 @@ class TrainPipeline:
         ``inline_graphs_supported()``); a forked graph (filter gradients on a side stream) is correct everywhere but its
         replays do not overlap - then the pipeline only hides the host's launch / read-back time."""
         self.inline = inline_graphs_supported() if inline is None else bool(inline)
-        self._checked = False
         self.net = net
         self.dev = torch.device(net._device)
         self.slots = max(1, int(slots))
@@ -500,28 +517,11 @@ class TrainPipeline:
             if len(self.runners[s]) >= self.max_graphs:
                 raise RuntimeError("TrainPipeline: more than %d distinct frame shapes" % self.max_graphs)
             torch.cuda.synchronize(self.dev)       # captures happen with the device idle
-            try:
-                runner = TrainStepRunner(self.net, key[0], key[1], key[2], key[3], info, grads=self.grads[s],
-                                         autotune=not any(self.runners), inline=self.inline, defer_bn_stats=True)
-            except InlineCaptureUnsafe as e:
-                import warnings
-                warnings.warn("TrainPipeline: %s; capturing forked graphs instead (correct, but replays of different slots do "
-                              "not overlap)" % e)
-                self.inline = False
-                runner = TrainStepRunner(self.net, key[0], key[1], key[2], key[3], info, grads=self.grads[s],
-                                         autotune=False, inline=False, defer_bn_stats=True)
-            self.runners[s][key] = runner
-            if self.inline:
-                # every newly captured single-chain runner proves that its replays reproduce each other (3 replays)
-                try:
-                    self._check_replays(runner, blobs, self.grads[s])
-                except RuntimeError as e:
-                    import warnings
-                    warnings.warn(str(e) + "  Falling back to forked graphs.")
-                    self.inline = False
-                    runner = self.runners[s][key] = TrainStepRunner(self.net, key[0], key[1], key[2], key[3], info,
-                                                                    grads=self.grads[s], autotune=False, inline=False,
-                                                                    defer_bn_stats=True)
+            # a single-chain runner proves that its replays reproduce each other; one fallback switches the whole pipeline
+            runner = self.runners[s][key] = capture_with_fallback(
+                self.net, blobs, self.inline, key[0], key[1], key[2], key[3], info, grads=self.grads[s],
+                autotune=not any(self.runners), defer_bn_stats=True)
+            self.inline = runner.inline
         st = self.streams[s]
         st.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(st):
@@ -540,9 +540,6 @@ class TrainPipeline:
         self.pending[s] = [runner, ev, None, None]
         self.order.append(s)
         return s
-
-    def _check_replays(self, runner, blobs, grads):
-        check_replays(self.net, runner, blobs, grads)
 
     def in_flight(self):
         return len(self.order)

@@ -10,6 +10,8 @@ convolution output that receives no gradient.  The LiDAR backbone trains its Bat
 (lib/nets/lidarnet.py:110,152-175): ``_BnTrainFn`` = ``frcnn_bn_train_fwd / _bwd``.  Activations are NHWC; parameters keep the reference's layouts
 (Conv2d (K,C,R,S), Linear (out,in)) and are re-laid out as KRSC through ``hip_modules.prepared_conv`` caches.
 """
+import collections
+import contextlib
 import os
 
 import torch
@@ -18,65 +20,80 @@ from .. import ops
 from .hip_modules import _winograd_filter, pad4, prepared_conv, stable_store
 
 
-# Filter gradients are off the critical path of backward (only the data gradient feeds the next node), so they CAN
-# run on a side HIP stream and be accumulated into ``param.grad`` there; ``join_weight_grads()`` (called by
-# Network.backward before clipping / the optimizer) makes the main stream wait for them.  Measured on the FPN train
-# step (round 1): no gain — the step is bound by GPU throughput, not by the dependency chain — so the default keeps
-# the plain autograd flow.
-ASYNC_WGRAD = False
-_SIDE = {}
-_KEEP = []      # operands of side-stream launches, held until the main stream has joined the side stream
+# How one pass launches its filter gradients.  They are off the critical path of backward (only the data gradient feeds the next
+# node), so a pass may accumulate them into ``param.grad`` itself instead of returning them to autograd;
+# ``join_weight_grads()`` (called by Network.backward before clipping / the optimizer) then completes them.
+#   accumulate    False: gradients go back to autograd, the other fields are not read.  True: this package's own launches add
+#                 into ``param.grad`` (a captured step: autograd's AccumulateGrad nodes run on the parameter's creation stream,
+#                 outside the capture).  Measured on the eager FPN step (round 1): no gain, the step is bound by GPU throughput.
+#   side_stream   True: on a side stream next to the data-gradient chain - a captured step is a forked graph.  False: in line on
+#                 the step's own stream - ONE chain of kernel nodes, the form the runtime overlaps when several replays are in
+#                 flight (model/train_graph.TrainPipeline: two replays of a forked graph were measured not to overlap at all;
+#                 train_graph.inline_graphs_supported and the replay check guard the runtime fault this form once hit).
+#   grouped       repeated layers of identical shape - the 22 equal Bottlenecks of layer3 - are collected per shape and launched
+#                 TOGETHER (ops.conv2d_bwd_weight_acc_grouped): one launch pair per shape instead of a pixel-split launch + a
+#                 slab reduction per layer.  A group is flushed when it is full, when its shape has not come up for _STALE calls
+#                 (its stage's backward is over), and at join_weight_grads().  The grouped launches run AFTER their stage's
+#                 data-gradient chain instead of next to it: with the register-staged kernel they lost (15.3-15.4 against
+#                 15.0-15.2 ms per replayed step, round 3); with conv_wgrad_dma_f32, which adds into param.grad itself, they win
+#                 (14.7 -> 14.3 ms, round 5).
+#   bn_stat_sink  {id(BatchNorm module): [mean buffer, variance buffer, used]} while a step with DEFERRED running statistics is
+#                 captured (model/train_graph.TrainStepRunner(defer_bn_stats=True)), else None: see _BnTrainFn.forward
+WgradSchedule = collections.namedtuple('WgradSchedule', 'accumulate side_stream grouped bn_stat_sink')
+EAGER_SCHEDULE = WgradSchedule(accumulate=False, side_stream=False, grouped=False, bn_stat_sink=None)
+SCHEDULE = EAGER_SCHEDULE       # a plain module global: autograd's backward thread has to see it too
 
 
-# True (default): filter gradients run on a side stream next to the data-gradient chain (a captured step is a forked graph).
-# False: in line on the step's own stream - a captured step is then ONE chain of kernel nodes, the form the runtime overlaps
-# when several replays are in flight on different streams (model/train_graph.TrainPipeline: two replays of a forked graph were
-# measured not to overlap at all).  ONLY with DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in the environment before the HIP runtime starts:
-# with ROCm 7's packet-captured replay of single-chain graphs this step's graph adds wrong filter gradients from its second
-# replay on (train_graph.inline_graphs_supported / TrainPipeline's replay check guard it).
-WGRAD_ON_SIDE_STREAM = True
+@contextlib.contextmanager
+def wgrad_schedule(schedule):
+    """Install ``schedule`` for the passes run inside; the previous one is back on exit, also when the body raises."""
+    global SCHEDULE
+    prev, SCHEDULE = SCHEDULE, schedule
+    try:
+        yield schedule
+    finally:
+        SCHEDULE = prev
 
 
-# Side streams per device.  Every parameter is pinned to ONE of them (first come, round robin): launches that accumulate into the
-# same gradient buffer - the RPN head applied to five pyramid levels - stay ordered, launches of different parameters may overlap.
+# Process-wide A/B switches (tools set them before anything is captured).
+# Side streams per device.  Every gradient buffer is pinned to ONE of them (first come, round robin): launches that accumulate into
+# the same buffer - the RPN head applied to five pyramid levels - stay ordered, launches into different buffers may overlap.
 WGRAD_SIDE_STREAMS = 1
 # captured steps: the BatchNorm backward adds d_gamma / d_beta into param.grad itself (False: temporaries + add_ launches; A/B)
 BN_GRADS_IN_KERNEL = os.environ.get('FRCNN_BN_GRADS_IN_KERNEL', '1') != '0'
-_STREAM_OF = {}    # (device, id of the gradient's owner) -> index
-
-
-def _side_stream(device, owner=None):
-    if not WGRAD_ON_SIDE_STREAM:
-        return torch.cuda.current_stream(device)
-    key = str(device)
-    pool = _SIDE.setdefault(key, [])
-    want = max(1, int(WGRAD_SIDE_STREAMS))
-    while len(pool) < want:
-        pool.append(torch.cuda.Stream(device=device))
-    if want == 1 or owner is None:
-        return pool[0]
-    idx = _STREAM_OF.get((key, owner))
-    if idx is None:
-        idx = _STREAM_OF[(key, owner)] = len(_STREAM_OF) % want
-    return pool[idx % want]
-
-
-# Deferred filter gradients (ASYNC_WGRAD and GROUP_WGRAD): repeated layers of identical shape - the 22 equal Bottlenecks of
-# layer3 - are collected per shape and launched TOGETHER (ops.conv2d_bwd_weight_acc_grouped): one launch pair per shape instead
-# of a pixel-split launch + a slab reduction per layer.  A group is flushed to the side stream when it is full, when its shape
-# has not come up for _STALE calls (its stage's backward is over), and at join_weight_grads().
-# OFF for the eager step; ON in every captured step since round 5 (model/train_graph.TrainStepRunner).  The grouped launches
-# are far more efficient (one unsplit launch per shape and stage) but run AFTER their stage's data-gradient chain instead of
-# next to it: with the register-staged kernel and its accumulation kernel they lost (15.3-15.4 against 15.0-15.2 ms per replayed
-# step, round 3); with conv_wgrad_dma_f32, which adds into param.grad itself, they win (14.7 -> 14.3 ms, round 5).
-GROUP_WGRAD = False
-# {id(BatchNorm module): (mean buffer, variance buffer)} while a training step with DEFERRED running statistics is captured
-# (model/train_graph.TrainStepRunner(defer_bn_stats=True)), else None: see _BnTrainFn.forward
-BN_STAT_SINK = None
 GROUP_WGRAD_SIZE = 24  # layers per grouped launch (<= ops.WGRAD_MAX_GROUPS): a whole ResNet stage
-_DEFER = {}          # key -> list of (x, d_conv, grad)
-_DEFER_AGE = {}      # key -> _wgrad calls since the key last came up
+_SIDE = {}         # device -> side streams
+_STREAM_OF = {}    # (device, id of the gradient's owner) -> index
+_KEEP = []         # operands of filter-gradient launches, held until the main stream has joined the side streams
+_DEFER = {}        # key -> list of (x, d_conv, grad)
+_DEFER_AGE = {}    # key -> _wgrad calls since the key last came up
 _STALE = 8
+
+
+def _launch_wgrad(owner, operands, launch):
+    """Run ``launch()`` where the installed schedule puts filter gradients: on the side stream ``owner`` is pinned to, ordered
+    after the main stream, or in line.  ``owner``: the gradient buffer the launch accumulates into (the parameter when it
+    has no in-place buffer), so that every launch into one buffer lands on one stream."""
+    device = operands[0].device
+    main = stream = torch.cuda.current_stream(device)
+    if SCHEDULE.side_stream:
+        pool = _SIDE.setdefault(str(device), [])
+        want = max(1, int(WGRAD_SIDE_STREAMS))
+        while len(pool) < want:
+            pool.append(torch.cuda.Stream(device=device))
+        pin = _STREAM_OF.setdefault((str(device), id(owner)), len(_STREAM_OF) % want) if want > 1 else 0
+        stream = pool[pin % want]
+        stream.wait_stream(main)
+    with torch.cuda.stream(stream):
+        launch()
+    # the side stream still reads the operands when this function's caller drops them, and the allocator would hand their
+    # blocks to the next main-stream allocation.  Tensor.record_stream covers that in eager mode; inside a stream capture it
+    # was observed not to (run-to-run different gradients from the replayed graph), so the operands are simply kept alive
+    # until join_weight_grads() has made the main stream wait for the side stream.
+    _KEEP.extend(operands)
+    if SCHEDULE.side_stream:
+        for t in operands:
+            t.record_stream(stream)
 
 
 def _flush_group(key):
@@ -84,23 +101,13 @@ def _flush_group(key):
     _DEFER_AGE.pop(key, None)
     if not entries:
         return
-    x0 = entries[0][0]
+    xs, ds, grads = [list(col) for col in zip(*entries)]
     r, s, stride, pad = key[2:6]
-    main = torch.cuda.current_stream(x0.device)
-    side = _side_stream(x0.device, id(entries[0][2]))
-    if WGRAD_ON_SIDE_STREAM:
-        side.wait_stream(main)
-    with torch.cuda.stream(side):
-        if len(entries) == 1:
-            ops.conv2d_bwd_weight_acc(entries[0][0], entries[0][1], r, s, entries[0][2], None, stride=stride, pad=pad)
-        else:
-            ops.conv2d_bwd_weight_acc_grouped([e[0] for e in entries], [e[1] for e in entries], r, s, [e[2] for e in entries],
-                                              stride=stride, pad=pad)
-    for x, d, _ in entries:
-        _KEEP.append((x, d))
-        if WGRAD_ON_SIDE_STREAM:
-            x.record_stream(side)
-            d.record_stream(side)
+    if len(entries) == 1:
+        launch = lambda: ops.conv2d_bwd_weight_acc(xs[0], ds[0], r, s, grads[0], None, stride=stride, pad=pad)
+    else:
+        launch = lambda: ops.conv2d_bwd_weight_acc_grouped(xs, ds, r, s, grads, stride=stride, pad=pad)
+    _launch_wgrad(grads[0], xs + ds, launch)
 
 
 def _defer_wgrad(x, d_conv, r, s, stride, pad, grad):
@@ -142,43 +149,38 @@ def _accumulate(param, grad):
         param.grad.add_(grad)
 
 
-def _wgrad(x, d_conv, r, s, stride, pad, targets):
-    """Filter (and bias) gradient of one convolution.  ``targets`` = list of (param, fn) where fn maps
-    (dw_krsc, db) to that parameter's gradient.  Synchronous mode returns the list of gradients; asynchronous mode
-    launches on the side stream, accumulates into param.grad there and returns None for each."""
-    want_bias = any(kind == 'b' for _, _, kind in targets)
-    if not ASYNC_WGRAD:
+def _wgrad(x, d_conv, r, s, stride, pad, weight=None, bias=None, mapped=None):
+    """Filter (and bias) gradient of one convolution, one list entry per target: the gradients when the schedule returns
+    them to autograd, None for each when it accumulates into param.grad.
+    Plain case: ``weight`` [, ``bias``] of ONE module (targets in that order), gradients in the parameters' own layout -
+    with the gradient buffers in place it is one launch chain that sums the pixel-split slabs, changes the layout and adds
+    into param.grad (no temporaries, no permute copy, no add_), and it may join a group.
+    Special layouts (the fused head's K-slices, the permuted Linear): ``mapped`` = list of (param, fn), fn maps
+    (dw_krsc, db) to that parameter's gradient; never in place, never grouped."""
+    plain = mapped is None
+    if plain:
+        mapped = [(weight, lambda dwk, dbk: _param_grad_from_krsc(dwk, weight))] if weight is not None else []
+        if bias is not None:
+            mapped.append((bias, lambda dwk, dbk: dbk))
+    want_bias = bias is not None or not plain
+
+    def param_layout_grads():
         dw_krsc, db = ops.conv2d_bwd_weight(x, d_conv, r, s, stride=stride, pad=pad, want_bias=want_bias)
-        return [fn(dw_krsc, db) for _, fn, _ in targets]
-    kinds = [kind for _, _, kind in targets]
-    direct = (kinds in (['w'], ['w', 'b']) and all(p.grad is not None and p.grad.is_contiguous() for p, _, _ in targets)
-              and targets[0][0].dim() in (2, 4) and targets[0][0].numel() == d_conv.shape[-1] * targets[0][0].shape[1] * r * s)
-    if GROUP_WGRAD and direct and kinds == ['w'] and targets[0][0].dim() == 4:
-        _defer_wgrad(x, d_conv, r, s, stride, pad, targets[0][0].grad)
-        return [None]
-    main = torch.cuda.current_stream(x.device)
-    side = _side_stream(x.device, id(targets[0][0]))
-    if WGRAD_ON_SIDE_STREAM:
-        side.wait_stream(main)
-    with torch.cuda.stream(side):
-        # plain Conv2d / Linear targets ('w' [+ 'b'] of one module, gradient buffers in place): one launch chain sums the
-        # pixel-split slabs, changes the layout and adds into param.grad - no temporaries, no permute copy, no add_
-        if direct:
-            ops.conv2d_bwd_weight_acc(x, d_conv, r, s, targets[0][0].grad, targets[1][0].grad if len(targets) > 1 else None,
-                                      stride=stride, pad=pad)
-        else:
-            dw_krsc, db = ops.conv2d_bwd_weight(x, d_conv, r, s, stride=stride, pad=pad, want_bias=want_bias)
-            for param, fn, _ in targets:
-                _accumulate(param, fn(dw_krsc, db))
-    # the side stream still reads x / d_conv when this function's caller drops them, and the allocator would hand their
-    # blocks to the next main-stream allocation.  Tensor.record_stream covers that in eager mode; inside a stream capture it
-    # was observed not to (run-to-run different gradients from the replayed graph), so the operands are simply kept alive
-    # until join_weight_grads() has made the main stream wait for the side stream.
-    _KEEP.append((x, d_conv))
-    if WGRAD_ON_SIDE_STREAM:
-        x.record_stream(side)
-        d_conv.record_stream(side)
-    return [None for _ in targets]
+        return [fn(dw_krsc, db) for _, fn in mapped]
+
+    if not SCHEDULE.accumulate:
+        return param_layout_grads()
+    in_place = (plain and weight is not None and all(p.grad is not None and p.grad.is_contiguous() for p, _ in mapped)
+                and weight.dim() in (2, 4) and weight.numel() == d_conv.shape[-1] * weight.shape[1] * r * s)
+    if in_place and SCHEDULE.grouped and bias is None and weight.dim() == 4:
+        _defer_wgrad(x, d_conv, r, s, stride, pad, weight.grad)
+    elif in_place:
+        _launch_wgrad(weight.grad, [x, d_conv], lambda: ops.conv2d_bwd_weight_acc(
+            x, d_conv, r, s, weight.grad, bias.grad if bias is not None else None, stride=stride, pad=pad))
+    else:
+        _launch_wgrad(mapped[0][0], [x, d_conv],
+                      lambda: [_accumulate(p, g) for (p, _), g in zip(mapped, param_layout_grads())])
+    return [None] * len(mapped)
 
 
 def _transposed_filter(conv_like, w_krsc):
@@ -262,16 +264,12 @@ class _ConvFn(torch.autograd.Function):
             d_conv, d_res = dy, None
         dx = dw = db = None
         r, s = w_krsc.shape[1], w_krsc.shape[2]
-        targets = []
-        if need_w:
-            targets.append((weight, lambda dwk, dbk, w=weight: _param_grad_from_krsc(dwk, w), 'w'))
-        if bias is not None and need_b:
-            targets.append((bias, lambda dwk, dbk: dbk, 'b'))
-        if targets:
-            grads = _wgrad(x, d_conv, r, s, stride, pad, targets)
+        need_b = need_b and bias is not None
+        if need_w or need_b:
+            grads = _wgrad(x, d_conv, r, s, stride, pad, weight if need_w else None, bias if need_b else None)
             if need_w:
                 dw = grads[0]
-            if bias is not None and need_b:
+            if need_b:
                 db = grads[-1]
         if need_x:
             w_t = _transposed_filter(owner, w_krsc)
@@ -288,7 +286,7 @@ class _BnTrainFn(torch.autograd.Function):
     def forward(ctx, y, residual, gamma, beta, bn, relu):
         track = bn.track_running_stats and bn.running_mean is not None
         momentum = bn.momentum
-        sink = BN_STAT_SINK.get(id(bn)) if (track and BN_STAT_SINK is not None) else None
+        sink = SCHEDULE.bn_stat_sink.get(id(bn)) if (track and SCHEDULE.bn_stat_sink is not None) else None
         if sink is not None:
             # deferred statistics (model/train_graph.TrainPipeline): this launch leaves the frame's batch mean / unbiased
             # variance in the slot's private buffers - momentum 1 turns the kernel's update (1 - m) * old + m * stat into
@@ -316,7 +314,7 @@ class _BnTrainFn(torch.autograd.Function):
     def backward(ctx, dout):
         y, out, gamma, mean, invstd = ctx.saved_tensors
         wprm, bprm = ctx.affine
-        if (ASYNC_WGRAD and BN_GRADS_IN_KERNEL and ctx.needs_input_grad[2] and ctx.needs_input_grad[3] and wprm is not None and bprm is not None
+        if (SCHEDULE.accumulate and BN_GRADS_IN_KERNEL and ctx.needs_input_grad[2] and ctx.needs_input_grad[3] and wprm is not None and bprm is not None
                 and wprm.grad is not None and bprm.grad is not None and wprm.grad.is_contiguous() and bprm.grad.is_contiguous()):
             # captured steps: d_gamma / d_beta are added into the parameters' gradient buffers by the BatchNorm backward's own
             # statistics pass (no temporaries, no add_ launches: 168 of the LiDAR step's launches)
@@ -327,7 +325,7 @@ class _BnTrainFn(torch.autograd.Function):
         dy, dres, dgamma, dbeta = ops.bn_train_bwd(dout.contiguous(), out, y, gamma.detach() if gamma is not None else None,
                                                    mean, invstd, relu=ctx.relu,
                                                    want_res=ctx.has_res and ctx.needs_input_grad[1])
-        if ASYNC_WGRAD:
+        if SCHEDULE.accumulate:
             # captured steps (model/train_graph.py) accumulate parameter gradients themselves, in place, on the step's stream:
             # autograd's AccumulateGrad nodes run on the parameters' creation stream, outside the capture
             with torch.no_grad():
@@ -402,7 +400,7 @@ class _PermutedLinearFn(torch.autograd.Function):
         d_conv = ops.act_bwd(dy4, y, None, relu=True)[0] if relu else dy4
         x4 = x2d.view(r, 1, 1, -1)
         to_w = lambda dwk, dbk: dwk.view(lin.out_features, p, p, c).permute(0, 3, 1, 2).reshape(lin.out_features, -1)
-        dw, db = _wgrad(x4, d_conv, 1, 1, 1, 0, [(lin.weight, to_w, 'w_perm'), (lin.bias, lambda dwk, dbk: dbk, 'b')])
+        dw, db = _wgrad(x4, d_conv, 1, 1, 1, 0, mapped=[(lin.weight, to_w), (lin.bias, lambda dwk, dbk: dbk)])
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.conv2d_bwd_data(d_conv, _transposed_filter(lin, w_krsc), tuple(x4.shape)).view(r, -1)
@@ -429,11 +427,11 @@ class _FusedHeadFn(torch.autograd.Function):
         dy = dy.contiguous()
         k1, k2 = w1.shape[0], w2.shape[0]
         b1, b2 = ctx.biases
-        dw1, db1, dw2, db2 = _wgrad(x, dy, w_krsc.shape[1], w_krsc.shape[2], 1, 0, [
-            (w1, lambda dwk, dbk: _param_grad_from_krsc(dwk[:k1], w1), 'w_part'),
-            (b1, lambda dwk, dbk: dbk[:k1].contiguous(), 'b'),
-            (w2, lambda dwk, dbk: _param_grad_from_krsc(dwk[k1:k1 + k2], w2), 'w_part'),
-            (b2, lambda dwk, dbk: dbk[k1:k1 + k2].contiguous(), 'b')])
+        dw1, db1, dw2, db2 = _wgrad(x, dy, w_krsc.shape[1], w_krsc.shape[2], 1, 0, mapped=[
+            (w1, lambda dwk, dbk: _param_grad_from_krsc(dwk[:k1], w1)),
+            (b1, lambda dwk, dbk: dbk[:k1].contiguous()),
+            (w2, lambda dwk, dbk: _param_grad_from_krsc(dwk[k1:k1 + k2], w2)),
+            (b2, lambda dwk, dbk: dbk[k1:k1 + k2].contiguous())])
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.conv2d_bwd_data(dy, _transposed_filter(owner, w_krsc), tuple(x.shape))
@@ -515,8 +513,7 @@ class _BottleneckFn(torch.autograd.Function):
         need_w = [w.requires_grad for w in (blk.conv1.weight, blk.conv2.weight, blk.conv3.weight)]
 
         def wg(inp, dz, conv, r, stride, pad):
-            w = conv.weight
-            return _wgrad(inp, dz, r, r, stride, pad, [(w, lambda dwk, dbk: _param_grad_from_krsc(dwk, w), 'w')])[0]
+            return _wgrad(inp, dz, r, r, stride, pad, conv.weight)[0]
 
         dz3, d_id = ops.act_bwd(dy.contiguous(), out, p3[1], relu=True, want_res=True)
         dw3 = wg(o2, dz3, blk.conv3, 1, 1, 0) if need_w[2] else None

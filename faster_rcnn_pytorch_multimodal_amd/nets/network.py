@@ -679,7 +679,7 @@ class Network(nn.Module):
                 prm.grad.clamp_(-clip, clip)
 
     def backward(self, loss):
-        """loss.backward() plus the join of the filter-gradient side stream (autograd_ops.ASYNC_WGRAD): afterwards every
+        """loss.backward() plus the join of the filter-gradient side stream (autograd_ops.WgradSchedule): afterwards every
         ``param.grad`` is complete as seen from the current stream."""
         try:
             loss.backward()

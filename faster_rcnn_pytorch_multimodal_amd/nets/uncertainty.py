@@ -320,13 +320,16 @@ class _MultiHeadFn(torch.autograd.Function):
         x, *params = ctx.saved_tensors
         w_krsc, _, owner, sizes = ctx.pack
         dy = dy.contiguous()
-        targets, lo = [], 0
-        for i, k in enumerate(sizes):
-            w, b = params[2 * i], params[2 * i + 1]
-            targets.append((w, lambda dwk, dbk, lo=lo, k=k, w=w: _param_grad_from_krsc(dwk[lo:lo + k], w), 'w'))
-            targets.append((b, lambda dwk, dbk, lo=lo, k=k: dbk[lo:lo + k].contiguous(), 'b'))
-            lo += k
-        grads = _wgrad(x, dy, 1, 1, 1, 0, targets)
+        if len(sizes) == 1 and sizes[0] == w_krsc.shape[0]:          # one head whose rows need no padding: a plain Linear
+            grads = _wgrad(x, dy, 1, 1, 1, 0, params[0], params[1])
+        else:
+            slices, lo = [], 0
+            for i, k in enumerate(sizes):
+                w, b = params[2 * i], params[2 * i + 1]
+                slices.append((w, lambda dwk, dbk, lo=lo, k=k, w=w: _param_grad_from_krsc(dwk[lo:lo + k], w)))
+                slices.append((b, lambda dwk, dbk, lo=lo, k=k: dbk[lo:lo + k].contiguous()))
+                lo += k
+            grads = _wgrad(x, dy, 1, 1, 1, 0, mapped=slices)
         dx = ops.conv2d_bwd_data(dy, _transposed_filter(owner, w_krsc), tuple(x.shape)) if ctx.needs_input_grad[0] else None
         return (dx, None) + tuple(grads)
 

@@ -2383,17 +2383,15 @@ def test_rpn_backward_on_labelled_pixels_equals_dense_backward(hip):
 
 
 def test_train_step_with_grouped_filter_gradients(hip):
-    """autograd_ops.GROUP_WGRAD (off by default): the filter gradients of a stage's equal Bottlenecks collected and launched
-    together give the per-layer gradients (res101+FPN step, side-stream mode as inside a captured step)."""
+    """autograd_ops.WgradSchedule(grouped=True): the filter gradients of a stage's equal Bottlenecks collected and launched
+    together give the per-layer gradients (res101+FPN step, side-stream schedule as inside a forked captured step)."""
     from faster_rcnn_pytorch_multimodal_amd.nets import autograd_ops as A
     net, _ = _build_fpn_pair(seed=23)
     data, info, gt, _, _ = _fpn_case()
     net.train()
     results = []
-    old = (A.GROUP_WGRAD, A.ASYNC_WGRAD)
-    try:
-        for grouped in (False, True):
-            A.GROUP_WGRAD, A.ASYNC_WGRAD = grouped, True
+    for grouped in (False, True):
+        with A.wgrad_schedule(A.WgradSchedule(accumulate=True, side_stream=True, grouped=grouped, bn_stat_sink=None)):
             for p in net.parameters():
                 if p.requires_grad:
                     p.grad = torch.zeros_like(p)
@@ -2403,8 +2401,7 @@ def test_train_step_with_grouped_filter_gradients(hip):
             torch.cuda.synchronize()
             assert not A._DEFER
             results.append({n_: p.grad.clone() for n_, p in net.named_parameters() if p.grad is not None})
-    finally:
-        A.GROUP_WGRAD, A.ASYNC_WGRAD = old
+    assert A.SCHEDULE is A.EAGER_SCHEDULE
     g_ref, g_grp = results
     floor = 0.01 * max(float(v.abs().max()) for v in g_ref.values())
     worst = max(float((g_grp[k] - g_ref[k]).abs().max()) / max(float(g_ref[k].abs().max()), floor) for k in g_ref)

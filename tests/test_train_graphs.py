@@ -474,3 +474,84 @@ def test_concurrent_streams_are_chosen_by_measurement(hip):
         assert not any(again.values()), again
     seven, distinct = S.concurrent_streams(7, DEV)                 # more streams than queues: as many distinct as there are
     assert len(seven) == 7 and 3 <= distinct <= 7
+
+
+def _replay_check_raising(monkeypatch, train_graph, error):
+    def check(net, runner, blobs, grads):
+        raise error
+
+    monkeypatch.setattr(train_graph, "check_replays", check)
+
+
+def test_replay_mismatch_falls_back_to_the_forked_capture(hip, monkeypatch):
+    """train_graph.capture_with_fallback: a single-chain capture whose replay check reports ``ReplayMismatch`` (substituted
+    here: the check raises on the host) is replaced, with ONE warning, by the forked capture - behind ``Network.train_step``
+    (``captured_step``: the forked runner's loss follows the eager step's) and in ``TrainPipeline`` (the whole pipeline
+    switches to forked graphs)."""
+    from faster_rcnn_pytorch_multimodal_amd.model import config as C
+    from faster_rcnn_pytorch_multimodal_amd.model import train_graph
+    _replay_check_raising(monkeypatch, train_graph, train_graph.ReplayMismatch("replays differ (substituted check)"))
+    net_e, _ = T._build_fpn_pair(seed=23)
+    net_g, _ = T._build_fpn_pair(seed=23)
+    data, info, gt, _, _ = T._fpn_case()
+    for n in (net_e, net_g):
+        n.train()
+    blobs = {"data": data, "info": info, "gt_boxes": gt, "gt_boxes_dc": np.zeros((0, 4), np.float32)}
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        runner = train_graph.captured_step(net_g, 256, 320, 3, len(gt), info, blobs)
+    assert len(seen) == 1 and "replays differ (substituted check)" in str(seen[0].message), [str(w.message) for w in seen]
+    assert not runner.inline
+    opt = torch.optim.SGD([p for p in net_e.parameters() if p.requires_grad], lr=1e-3)
+    opt.zero_grad(set_to_none=False)
+    torch.manual_seed(600)
+    loss_e = net_e.train_step(blobs, opt, update_weights=False)
+    torch.manual_seed(600)
+    loss_g = float(runner.run(blobs)[0])
+    assert abs(loss_e - loss_g) <= 2e-5 * max(1.0, abs(loss_e)), (loss_e, loss_g)
+    pipe = train_graph.TrainPipeline(net_g, slots=1)
+    assert pipe.inline
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        pipe.submit(blobs)
+    loss_p, _ = pipe.collect()
+    pipe.flush()
+    assert len(seen) == 1 and np.isfinite(loss_p)
+    assert not pipe.inline and [r.inline for r in pipe.runners[0].values()] == [False]
+    C.reset_cfg()
+
+
+def test_other_errors_of_the_replay_check_propagate_and_leave_no_trace(hip, monkeypatch):
+    """Only ``InlineCaptureUnsafe`` and ``ReplayMismatch`` choose the forked capture: any other error of the check (here a
+    substituted RuntimeError("boom")) reaches the caller of ``captured_step`` / ``TrainPipeline.submit`` - with every
+    ``param.grad`` still the parameter's own buffer holding its bits, no deferred filter-gradient group and the eager
+    schedule installed."""
+    from faster_rcnn_pytorch_multimodal_amd.model import config as C
+    from faster_rcnn_pytorch_multimodal_amd.model import train_graph
+    from faster_rcnn_pytorch_multimodal_amd.nets import autograd_ops
+    _replay_check_raising(monkeypatch, train_graph, RuntimeError("boom"))
+    net, _ = T._build_fpn_pair(seed=23)
+    net.train()
+    data, info, gt, _, _ = T._fpn_case()
+    blobs = {"data": data, "info": info, "gt_boxes": gt, "gt_boxes_dc": np.zeros((0, 4), np.float32)}
+    params = [p for p in net.parameters() if p.requires_grad]
+    g = torch.Generator().manual_seed(5)
+    for p in params:
+        p.grad = torch.randn(p.shape, generator=g).to(DEV)
+    own = [p.grad for p in params]
+    before = [t.clone() for t in own]
+    pipe = train_graph.TrainPipeline(net, slots=1)
+    calls = (lambda: train_graph.captured_step(net, 256, 320, 3, len(gt), info, blobs), lambda: pipe.submit(blobs))
+    for call in calls:
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")                      # no fallback: nothing warns
+            with pytest.raises(RuntimeError, match="^boom$") as raised:
+                call()
+        assert type(raised.value) is RuntimeError
+        torch.cuda.synchronize()
+        assert all(p.grad is o for p, o in zip(params, own))
+        assert all(torch.equal(o, b) for o, b in zip(own, before))
+        assert not autograd_ops._DEFER
+        assert autograd_ops.SCHEDULE is autograd_ops.EAGER_SCHEDULE
+    assert pipe.inline and not pipe.runners[0]                  # the pipeline did not switch, and kept no runner
+    C.reset_cfg()

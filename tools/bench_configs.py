@@ -309,7 +309,6 @@ def main():
     ap.add_argument("--rpn-dense-backward", action="store_true", help="A/B: dense backward through the RPN head")
     ap.add_argument("--no-dgrad-winograd-cache", action="store_true", help="A/B: transform the data-gradient filter per call")
     ap.add_argument("--no-fuse-act-bwd", action="store_true", help="A/B: separate frcnn_act_bwd passes inside the Bottleneck backward")
-    ap.add_argument("--group-wgrad", action="store_true", help="A/B: grouped filter-gradient launches per ResNet stage (autograd_ops.GROUP_WGRAD)")
     ap.add_argument("--group-wgrad-size", type=int, default=0, help="A/B: layers per grouped filter-gradient launch")
     ap.add_argument("--wgrad-variant", type=int, default=0, help="A/B: frcnn_conv2d_wgrad_set_variant (1 register-staged kernels, 2 LDS-DMA)")
     ap.add_argument("--plans", default="", help="import a convolution plan table (bench.py --plans / profiles/r05_plans.json) before running")
@@ -332,9 +331,6 @@ def main():
     if args.group_wgrad_size:
         from faster_rcnn_pytorch_multimodal_amd.nets import autograd_ops as _a4
         _a4.GROUP_WGRAD_SIZE = args.group_wgrad_size
-    if args.group_wgrad:
-        from faster_rcnn_pytorch_multimodal_amd.nets import autograd_ops as _a3
-        _a3.GROUP_WGRAD = True
     if args.no_fuse_act_bwd:
         from faster_rcnn_pytorch_multimodal_amd.nets import autograd_ops as _a2
         _a2.FUSE_ACT_BWD = False
