@@ -378,7 +378,8 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const float* __restrict__
       const float we = e < 8 ? opt.w[e] : 1.f;
       if (bbox_var) {
         // aleatoric attenuation (loss_utils.py:82-85): (0.5 * loss * exp(-s) + 0.5 * s) * inside, s = predicted log-variance
-        const float sv = bbox_var[o], ev = expf(-sv);
+        // exp_f32 (correctly rounded, like the log-sum-exp above): expf's last-ulp error is multiplied into dbox / dvar
+        const float sv = bbox_var[o], ev = exp_f32(-sv);
         const float l = huber1(diff) * we;
         rowsum += outside[o] * ((0.5f * l * ev + 0.5f * sv) * inside[o]);
         if (dbox) dbox[o] = g_box / (float)R * outside[o] * inside[o] * (0.5f * ev) * (huber1_grad(diff) * we) * chain;

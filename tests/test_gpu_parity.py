@@ -1,5 +1,6 @@
 """GPU parity tests: every HIP kernel, called through the C ABI (ops.py -> ctypes -> libfrcnn_hip.so),
 against the CPU oracle / a plain PyTorch-CPU fp32 reference on the same seeded inputs.
+The loss, Monte-Carlo statistics and small training kernels are taken to their edges in tests/test_loss_stat_kernels.py.
 
 Bars: bit-exact for indices, orders and keep masks; <= 1e-4 abs on box / score tensors; feature tensors
 (unbounded magnitude) within 2e-5 of the tensor's max magnitude (fp32 accumulation-order noise).
