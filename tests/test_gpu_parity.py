@@ -1631,7 +1631,9 @@ def roi_bwd_form(request):
 def test_roi_align_bwd_planned_equals_per_sample(hip):
     """frcnn_roi_align_bwd_planned against frcnn_roi_align_bwd on RoIs of every kind the plan distinguishes: small (light
     items), frame-sized (heavy items split into row bins), off-map, clipped at the border, a level mask and a device count;
-    150 x 250 map (more than 64 columns: several column chunks) and 75 rows (two row chunks)."""
+    150 x 250 and 75 x 40 maps (more than 64 rows: several row chunks).  A bin's columns are walked in chunks of 64 relative
+    to the bin's first column, and the widest bin here spans 36 columns, so this test stays in the first column chunk; bins
+    wider than 64 columns and an element-wise float64 reference are in tests/test_roi_align_kernels.py."""
     ops = _ops()
     g = torch.Generator().manual_seed(33)
     for (h, w, c, scale) in ((150, 250, 64, 0.25), (75, 40, 256, 1 / 16.0)):
