@@ -151,10 +151,11 @@ def extract_uncertainties(bbox_elem, splitlines, num_classes=2):
 
 
 # ---- waymo_eval.py:44-247 -------------------------------------------------------------------------------------------------
-def waymo_eval(detfile, class_recs, ovthresh=0.5, eval_type='2d', d_levels=2, bbox_elem=None, ignore_dc=None):
+def waymo_eval(detfile, class_recs, ovthresh=0.5, eval_type='2d', d_levels=2, bbox_elem=None, ignore_dc=None, device=None):
     """Returns (mrec, mprec, map) exactly as the reference does (three views of ONE array holding the AP per difficulty
     level, see the module docstring) plus a dict with the un-aliased quantities: {'ap', 'mean_recall', 'mean_precision',
-    'tp', 'fp', 'npos'}."""
+    'tp', 'fp', 'npos'}.  ``device='cuda'``: overlaps and matching come from one ``frcnn_eval_match`` launch and the tail
+    is vectorised (datasets/device_eval.py); same results, and the dict also carries 'jmax', 'ovmax' and 'code' per row."""
     ovthresh_dc = 0.5
     bbox_elem = bbox_elem if bbox_elem is not None else cfg[cfg.NET_TYPE.upper()].NUM_BBOX_ELEM
     ignore_dc = bool(cfg.TEST.get('IGNORE_DC', False)) if ignore_dc is None else ignore_dc
@@ -173,6 +174,10 @@ def waymo_eval(detfile, class_recs, ovthresh=0.5, eval_type='2d', d_levels=2, bb
                     for lvl in range(d_levels):
                         if rec["difficulty"][j] <= lvl + 1:
                             npos[i, lvl] += 1
+    if device is not None:
+        from .device_eval import evaluate_on_device
+        return evaluate_on_device(frame_tokens, confidence, bb_all, class_recs, ovthresh, eval_type, ignore_dc, d_levels,
+                                  npos, 1, device)
     for rec in class_recs:
         if 'hit' in rec:
             rec['hit'][:] = False

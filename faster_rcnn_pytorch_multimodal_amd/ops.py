@@ -970,6 +970,81 @@ def image_augment(img, aug, out=None, scratch=None, seed_dev=None, debug_pre=Non
     return out
 
 
+# frcnn_eval_match: eval types, verdict codes and the kernel's two sizes (include/frcnn_hip.h FRCNN_EVAL_*)
+EVAL_TYPES = {'2d': 0, 'bev_aa': 1, 'bev': 2, '3d': 3}
+EVAL_NONE, EVAL_TP, EVAL_DUP_FP, EVAL_FP = 0, 1, 2, 3
+EVAL_CHUNK, EVAL_LDS_GT = 64, 2048
+
+
+def eval_match(det_boxes, det_rows, det_offsets, gt_boxes, gt_ignore, gt_difficulty, gt_offsets, eval_type, ovthresh,
+               ovthresh_dc=0.5, dc_boxes=None, dc_offsets=None, max_gt_per_frame=None):
+    """Overlaps and matching of one class's detections against the ground truth, all frames in one launch
+    (frcnn_eval_match; lib/datasets/waymo_eval.py:131-213 and the same loop of kitti_eval.py / cadc_eval.py).
+    Device tensors grouped by frame: ``det_boxes`` (D, E) float64 with E = 4 for '2d' and 7 otherwise, ``det_rows`` (D,)
+    int32, ``gt_boxes`` (G, E) float64, ``gt_ignore`` (G,) uint8 or bool, ``gt_difficulty`` (G,) int32, the offsets
+    (F + 1,) int32; ``dc_boxes`` (C, E) / ``dc_offsets`` or None.  ``max_gt_per_frame``: the largest gt count of a frame
+    (read back from ``gt_offsets`` when not given: one host synchronisation).
+    Returns ``(code, jmax, ovmax, ovmax_dc, det_difficulty, hit)``: int32, int32, float64, float64, int32 per detection
+    and uint8 per gt box."""
+    lib = _hip.load()
+    if eval_type not in EVAL_TYPES:
+        raise _hip.HipError("eval_match: eval_type %r, one of %s" % (eval_type, sorted(EVAL_TYPES)))
+    elem = 4 if eval_type == '2d' else 7
+
+    def dev(t, name, dtypes, cols=None):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _hip.HipError("eval_match: %s must be a tensor on the MI355X (got %s); this package has no CPU path"
+                                % (name, getattr(t, "device", type(t))))
+        if t.dtype not in dtypes or not t.is_contiguous():
+            raise _hip.HipError("eval_match: %s must be contiguous %s (got %s)" % (name, dtypes[0], t.dtype))
+        if (t.dim() != 1) if cols is None else (t.dim() != 2 or t.shape[1] != cols):
+            raise _hip.HipError("eval_match: %s must have shape %s for eval_type %r, got %s"
+                                % (name, "(n,)" if cols is None else "(n, %d)" % cols, eval_type, tuple(t.shape)))
+        return t
+
+    dev(det_boxes, "det_boxes", (torch.float64,), elem)
+    dev(gt_boxes, "gt_boxes", (torch.float64,), elem)
+    num_det, num_gt = int(det_boxes.shape[0]), int(gt_boxes.shape[0])
+    dev(det_rows, "det_rows", (torch.int32,))
+    dev(gt_ignore, "gt_ignore", (torch.uint8, torch.bool))
+    dev(gt_difficulty, "gt_difficulty", (torch.int32,))
+    dev(det_offsets, "det_offsets", (torch.int32,))
+    dev(gt_offsets, "gt_offsets", (torch.int32,))
+    num_frames = int(det_offsets.numel()) - 1
+    if num_frames < 0 or gt_offsets.numel() != num_frames + 1:
+        raise _hip.HipError("eval_match: det_offsets and gt_offsets must both hold frames + 1 entries (got %d and %d)"
+                            % (det_offsets.numel(), gt_offsets.numel()))
+    if det_rows.numel() != num_det or gt_ignore.numel() != num_gt or gt_difficulty.numel() != num_gt:
+        raise _hip.HipError("eval_match: det_rows / gt_ignore / gt_difficulty must have one entry per box")
+    if (dc_boxes is None) != (dc_offsets is None):
+        raise _hip.HipError("eval_match: dc_boxes and dc_offsets go together")
+    num_dc = 0
+    if dc_boxes is not None:
+        dev(dc_boxes, "dc_boxes", (torch.float64,), elem)
+        dev(dc_offsets, "dc_offsets", (torch.int32,))
+        num_dc = int(dc_boxes.shape[0])
+        if dc_offsets.numel() != num_frames + 1:
+            raise _hip.HipError("eval_match: dc_offsets must hold frames + 1 entries")
+    if max_gt_per_frame is None:
+        max_gt_per_frame = int((gt_offsets[1:] - gt_offsets[:-1]).max().item()) if num_frames > 0 else 0
+    device = det_boxes.device
+    code = torch.empty(num_det, dtype=torch.int32, device=device)
+    jmax = torch.empty(num_det, dtype=torch.int32, device=device)
+    ovmax = torch.empty(num_det, dtype=torch.float64, device=device)
+    ovmax_dc = torch.empty(num_det, dtype=torch.float64, device=device)
+    dif = torch.empty(num_det, dtype=torch.int32, device=device)
+    hit = torch.zeros(num_gt, dtype=torch.uint8, device=device)
+    nbytes = lib.frcnn_eval_match_ws_bytes(num_gt, int(max_gt_per_frame))
+    ws = _workspace(nbytes, device) if nbytes else None
+    _hip.check(lib.frcnn_eval_match(_ptr(det_boxes), _ptr(det_rows), _ptr(det_offsets), num_det, _ptr(gt_boxes),
+                                    _ptr(gt_ignore), _ptr(gt_difficulty), _ptr(gt_offsets), num_gt, _ptr(dc_boxes),
+                                    _ptr(dc_offsets), num_dc, num_frames, EVAL_TYPES[eval_type], float(ovthresh),
+                                    float(ovthresh_dc), int(max_gt_per_frame), _ptr(code), _ptr(jmax), _ptr(ovmax),
+                                    _ptr(ovmax_dc), _ptr(dif), _ptr(hit), _ptr(ws), nbytes, _stream()),
+               "frcnn_eval_match")
+    return code, jmax, ovmax, ovmax_dc, dif, hit
+
+
 # ----------------------------------------------------------------------------------------------
 # training path
 # ----------------------------------------------------------------------------------------------

@@ -491,6 +491,47 @@ int frcnn_image_augment(const uint8_t* img_hwc3, int h, int w, int flip, int num
                         const float* stage_params_host, uint32_t seed, const uint32_t* seed_dev, void* scratch,
                         size_t scratch_bytes, uint8_t* out, float* debug_pre, void* stream);
 
+/* Scoring of one class's detections file: the overlap and matching loop the three evaluators share
+ * (lib/datasets/waymo_eval.py:131-213, kitti_eval.py:116-215, cadc_eval.py:115-206, and the iou helper of the missing
+ * lib/utils/eval_utils.py as restated in datasets/waymo_eval.py), one launch, one workgroup per frame.
+ * All arrays are device arrays grouped by frame (CSR): frame f owns detections det_offsets[f] .. det_offsets[f+1]-1, gt
+ * boxes gt_offsets[f] .. and don't-care boxes dc_offsets[f] .. (offsets: num_frames + 1 ints, ascending, last = count).
+ *   det_boxes (num_det, E) double, E = 4 for FRCNN_EVAL_2D ([x1,y1,x2,y2]) and 7 otherwise ([xc,yc,zc,l,w,h,ry]);
+ *   det_rows  (num_det) the detection's rank in the confidence order among detections that have a record (the
+ *             reference's idx counter), distinct, and ascending inside a frame;
+ *   gt_boxes (num_gt, E) double, gt_ignore (num_gt) bytes, gt_difficulty (num_gt) ints;
+ *   dc_boxes (num_dc, E) double; dc_boxes NULL or num_dc 0: don't-care boxes are not consulted (cfg.TEST.IGNORE_DC off).
+ * Per detection: ovmax = the largest overlap with the frame's gt boxes (-inf without any), jmax = the FIRST index inside
+ * the frame that attains it (np.argmax; 0 without gt), ovmax_dc = the largest overlap with the frame's don't-care boxes
+ * (0 without any), det_difficulty = gt_difficulty of jmax for codes 1 and 2 (else -1), and code:
+ *   FRCNN_EVAL_NONE    counts for nothing (candidate of an ignored gt; above the don't-care threshold; frame without gt)
+ *   FRCNN_EVAL_TP      candidate (ovmax > ovthresh, ovmax_dc < ovthresh_dc) with the smallest row among its gt's candidates
+ *   FRCNN_EVAL_DUP_FP  any other candidate of that gt: false positive at the levels of the gt's difficulty
+ *   FRCNN_EVAL_FP      no candidate, ovmax_dc < ovthresh_dc, frame has gt: false positive at every level
+ * Per gt box: hit = some candidate matched it (what the host loop leaves in rec['hit']).
+ * Overlaps are computed in double, term for term as datasets/waymo_eval.py iou (cos / sin of ry are the device's).
+ * Box values must be finite and, for the three LiDAR types, l, w, h > 0: the caller checks (datasets/device_eval.py).
+ * Any number of boxes per frame; a frame with more than FRCNN_EVAL_LDS_GT gt boxes keeps its per-gt row minimum in ws:
+ * pass max_gt_per_frame (the largest gt count of a frame) to both calls, ws_bytes() is 0 below that count.  Frames whose gt
+ * count exceeds FRCNN_EVAL_LDS_GT although max_gt_per_frame said otherwise get code -1 and are not scored.
+ * gt boxes pass through LDS FRCNN_EVAL_CHUNK at a time.  No allocation, no host synchronisation, one kernel launch. */
+#define FRCNN_EVAL_2D 0
+#define FRCNN_EVAL_BEV_AA 1
+#define FRCNN_EVAL_BEV 2
+#define FRCNN_EVAL_3D 3
+#define FRCNN_EVAL_NONE 0
+#define FRCNN_EVAL_TP 1
+#define FRCNN_EVAL_DUP_FP 2
+#define FRCNN_EVAL_FP 3
+#define FRCNN_EVAL_CHUNK 64
+#define FRCNN_EVAL_LDS_GT 2048
+size_t frcnn_eval_match_ws_bytes(int num_gt, int max_gt_per_frame);
+int frcnn_eval_match(const double* det_boxes, const int* det_rows, const int* det_offsets, int num_det,
+                     const double* gt_boxes, const uint8_t* gt_ignore, const int* gt_difficulty, const int* gt_offsets,
+                     int num_gt, const double* dc_boxes, const int* dc_offsets, int num_dc, int num_frames, int eval_type,
+                     double ovthresh, double ovthresh_dc, int max_gt_per_frame, int* code, int* jmax, double* ovmax,
+                     double* ovmax_dc, int* det_difficulty, uint8_t* hit, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training path (BASELINE config 4: FPN forward + backward of one train_step, lib/model/train_val.py:458)
  * ------------------------------------------------------------------------------------------- */
