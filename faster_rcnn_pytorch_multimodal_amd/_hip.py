@@ -86,6 +86,8 @@ PROTOTYPES = {
     "frcnn_bev_voxelize_ws_bytes": (c_size_t, [c_int, POINTER(c_float), POINTER(c_float), c_int]),
     "frcnn_bev_voxelize": (c_int, [_P, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_int, c_int, c_int,
                                    c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "frcnn_bev_voxelize_h": (c_int, [_P, c_int, c_int, POINTER(c_float), POINTER(c_float), c_double, c_float, c_int, c_int,
+                                     c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "frcnn_lidar_augment": (c_int, [_P, c_int, c_int, POINTER(c_float), ctypes.c_uint, POINTER(c_float), c_uint32, _P, _P, _P,
                                     c_int, _P]),
     "frcnn_lidar_augment_fov": (c_int, [_P, c_int, c_int, POINTER(c_float), ctypes.c_uint, POINTER(c_float), c_uint32, _P, _P,

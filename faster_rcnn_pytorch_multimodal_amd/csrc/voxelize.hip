@@ -5,7 +5,8 @@
 //   for each point in file order: cell = floor((p - range_min) / voxel_size) (fp32), dropped when outside the grid;
 //   a cell seen for the first time becomes voxel number `voxel_num` unless max_voxels voxels already exist (then the
 //   point is skipped); a voxel keeps its first max_points points.
-//   bev[x, y, z]            = max z of the voxel's points - z * VOXEL_HEIGHT                    (height slices)
+//   bev[x, y, z]            = max z of the voxel's points - z * VOXEL_HEIGHT                    (height slices;
+//                             int32 * Python float: float64, rounded once on the store into the fp32 map)
 //   bev[x, y, NUM_SLICES]   = num_points / MAX_PTS_PER_VOXEL                                     (density)
 //   bev[x, y, NUM_SLICES+1] = tanh(sum(intensity) / num_points)       (+2: same for elongation, or tanh(0) = 0)
 //   the meta channels are written per VOXEL into the (x, y) column, so the voxel created last in a column wins;
@@ -31,7 +32,7 @@ struct VoxParams {
   int grid[3];        // gx, gy, gz
   float z_shift;      // source_bin[:, 2] -= cfg.LIDAR.Z_RANGE[0]
   int n, f, max_points, max_voxels, num_slices, num_meta, elong_col;
-  float voxel_height;
+  double voxel_height;      // cfg.LIDAR.VOXEL_HEIGHT as the caller holds it; vsize[2] is its fp32 rounding
 };
 
 constexpr int NO_POINT = 0x7F7F7F7F;   // hipMemset pattern of the cell table
@@ -143,7 +144,8 @@ __global__ __launch_bounds__(256) void vox_feature_kernel(const float* __restric
   if (v >= V) return;
   const int n = cnt[v], base = off[v];
   const int keep = min(n, p.max_points);
-  float zmax = 0.f;                 // np.amax over the zero-initialised (max_points, F) voxel buffer
+  // np.amax over the zero-initialised (max_points, F) voxel buffer: a voxel that is not full has rows of zeros
+  float zmax = keep < p.max_points ? 0.f : -INFINITY;
   float isum = 0.f, esum = 0.f;
   int prev = -1;
   for (int k = 0; k < keep; ++k) {
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(256) void vox_feature_kernel(const float* __restric
   const int cx = id % p.grid[0], cy = (id / p.grid[0]) % p.grid[1], cz = id / (p.grid[0] * p.grid[1]);
   const int C = p.num_slices + p.num_meta;
   float* px = bev + ((size_t)cy * p.grid[0] + cx) * C;          // (y, x, c): the reference's final transpose
-  if (cz < p.num_slices) px[cz] = zmax - (float)cz * p.voxel_height;
+  if (cz < p.num_slices) px[cz] = (float)((double)zmax - (double)cz * p.voxel_height);   // the reference's float64
   atomicMax(col_last + cy * p.grid[0] + cx, v);
   vfeat[(size_t)v * 4 + 0] = (float)((double)keep / (double)p.max_points);
   vfeat[(size_t)v * 4 + 1] = (float)tanh((double)isum / (double)keep);
@@ -237,15 +239,18 @@ extern "C" size_t frcnn_bev_voxelize_ws_bytes(int num_points, const float* pc_ra
   return vox_layout(num_points, (long)g[0] * g[1] * g[2], (long)g[0] * g[1], max_voxels).bytes;
 }
 
-extern "C" int frcnn_bev_voxelize(const float* points, int num_points, int point_stride, const float* pc_range_host,
-                                  const float* voxel_size_host, float z_shift, int max_points, int max_voxels,
-                                  int num_slices, int num_meta, int elongation_col, float* bev, int* num_voxels,
-                                  void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int frcnn_bev_voxelize_h(const float* points, int num_points, int point_stride, const float* pc_range_host,
+                                    const float* voxel_size_host, double voxel_height, float z_shift, int max_points,
+                                    int max_voxels, int num_slices, int num_meta, int elongation_col, float* bev,
+                                    int* num_voxels, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   FRCNN_REQUIRE(points && pc_range_host && voxel_size_host && bev && num_points > 0 && point_stride >= 4 &&
                     max_points > 0 && max_voxels > 0 && num_slices > 0 && num_meta >= 0 && num_meta <= 3 &&
                     elongation_col < point_stride,
                 "bev_voxelize: bad arguments (points are rows of >= 4 floats x,y,z,intensity)");
+  FRCNN_REQUIRE((float)voxel_height == voxel_size_host[2],
+                "bev_voxelize: voxel_height %.17g is not the double that voxel_size[2] = %.9g was rounded from",
+                voxel_height, (double)voxel_size_host[2]);
   VoxParams p;
   FRCNN_REQUIRE(grid_of(pc_range_host, voxel_size_host, p.grid), "bev_voxelize: empty or oversized grid");
   FRCNN_REQUIRE(p.grid[2] <= num_slices, "bev_voxelize: %d z cells but %d height slices", p.grid[2], num_slices);
@@ -255,7 +260,7 @@ extern "C" int frcnn_bev_voxelize(const float* points, int num_points, int point
   p.fmax[0] = pc_range_host[3]; p.fmax[1] = pc_range_host[4]; p.fmax[2] = pc_range_host[5] + z_shift;
   p.n = num_points; p.f = point_stride; p.max_points = max_points; p.max_voxels = max_voxels;
   p.num_slices = num_slices; p.num_meta = num_meta; p.elong_col = elongation_col;
-  p.voxel_height = voxel_size_host[2];
+  p.voxel_height = voxel_height;
   const long cells = (long)p.grid[0] * p.grid[1] * p.grid[2], cols = (long)p.grid[0] * p.grid[1];
   const VoxLayout l = vox_layout(num_points, cells, cols, max_voxels);
   if (!ws || ws_bytes < l.bytes) return fail(FRCNN_ERR_WS, "bev_voxelize: workspace %zu < %zu bytes", ws_bytes, l.bytes);
@@ -289,4 +294,14 @@ extern "C" int frcnn_bev_voxelize(const float* points, int num_points, int point
     if (e != hipSuccess) return fail(FRCNN_ERR_LAUNCH, "bev_voxelize: copy voxel count: %s", hipGetErrorString(e));
   }
   return FRCNN_OK;
+}
+
+extern "C" int frcnn_bev_voxelize(const float* points, int num_points, int point_stride, const float* pc_range_host,
+                                  const float* voxel_size_host, float z_shift, int max_points, int max_voxels,
+                                  int num_slices, int num_meta, int elongation_col, float* bev, int* num_voxels,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  FRCNN_REQUIRE(voxel_size_host, "bev_voxelize: bad arguments (null voxel size)");
+  return frcnn_bev_voxelize_h(points, num_points, point_stride, pc_range_host, voxel_size_host,
+                              (double)voxel_size_host[2], z_shift, max_points, max_voxels, num_slices, num_meta,
+                              elongation_col, bev, num_voxels, ws, ws_bytes, stream);
 }

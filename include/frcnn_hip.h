@@ -393,7 +393,12 @@ int frcnn_filter_per_class(float* pred_boxes, const float* cls_prob, const int* 
  * pc_range_host[6] = [xmin,ymin,zmin,xmax,ymax,zmax] AFTER the reference's shift (zmin = 0, zmax = Z1 - Z0),
  * z_shift = cfg.LIDAR.Z_RANGE[0] (subtracted from every z), voxel_size_host[3]; grid = round((max-min)/size).
  * spconv VoxelGeneratorV2 semantics restated (third party, absent: parity unpinned): voxels numbered by first
- * appearance, at most max_voxels, each keeps its first max_points points.  Height slice = max z - slice*voxel height;
+ * appearance, at most max_voxels, each keeps its first max_points points.  Height slice = max z - slice*voxel height,
+ * evaluated like the reference's numpy expression (minibatch.py:467, int32 * Python float): in float64 from the fp32
+ * max z and the DOUBLE voxel height, rounded once to fp32.  frcnn_bev_voxelize_h takes that double (cfg.LIDAR.
+ * VOXEL_HEIGHT as the caller holds it; it must round to voxel_size_host[2]) and is exact for every height;
+ * frcnn_bev_voxelize is the same call with voxel_height = (double)voxel_size_host[2], which is the configured value
+ * only when that is an fp32 number (the default 0.5 is; 0.4 is not).
  * meta channels (density, tanh(mean intensity), tanh(mean elongation) or 0 when elongation_col < 0): the voxel
  * created last in a column wins.  num_voxels (device int, may be NULL) = occupied cells before the max_voxels cap. */
 int frcnn_bev_voxelize_grid(const float* pc_range_host, const float* voxel_size_host, int* grid_host);
@@ -403,6 +408,10 @@ int frcnn_bev_voxelize(const float* points, int num_points, int point_stride, co
                        const float* voxel_size_host, float z_shift, int max_points, int max_voxels, int num_slices,
                        int num_meta, int elongation_col, float* bev, int* num_voxels, void* ws, size_t ws_bytes,
                        void* stream);
+int frcnn_bev_voxelize_h(const float* points, int num_points, int point_stride, const float* pc_range_host,
+                         const float* voxel_size_host, double voxel_height, float z_shift, int max_points,
+                         int max_voxels, int num_slices, int num_meta, int elongation_col, float* bev, int* num_voxels,
+                         void* ws, size_t ws_bytes, void* stream);
 
 /* LiDAR point-cloud augmentation and test-time rain simulation (lib/roi_data_layer/minibatch.py:274-428), the per-point
  * transforms in front of frcnn_bev_voxelize, one pass in the reference's order: filter_points on the raw point
