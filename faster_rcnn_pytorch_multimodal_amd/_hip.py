@@ -151,6 +151,7 @@ PROTOTYPES = {
     "frcnn_filter_per_class_ws_bytes": (c_size_t, [c_int, c_int]),
     "frcnn_filter_per_class": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int,
                                        c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "frcnn_sgd_update": (c_int, [_P, _P, c_int64, _P, _P, c_int, _P, c_int64, c_float, c_float, c_int, _P]),
 }
 
 

@@ -33,6 +33,7 @@ SOURCES = {
     "lidar_augment.hip": ["-ffp-contract=off"],
     "image_augment.hip": ["-ffp-contract=off"],
     "eval_match.hip": ["-ffp-contract=off"],
+    "optim.hip": ["-ffp-contract=off"],
 }
 COMMON_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -65,6 +65,7 @@ def _defaults():
         # not in the reference: how SolverWrapper executes a step (model/train_graph.py)
         GRAPHS=True,             # replay each training step as a captured hipGraph (False: eager autograd launches)
         FRAMES_IN_FLIGHT=4,      # frames of a pseudo batch in flight as single-chain graphs, one per hardware queue (1: one captured step at a time)
+        FUSED_UPDATE=False,      # the weight update as one HIP launch over the gradient bucket (model/train_val.FusedSGD) instead of torch.optim.SGD
         LIDAR=dict(BBOX_NORMALIZE_MEANS=(0.0,) * 7, BBOX_NORMALIZE_STDS=(0.1, 0.1, 0.1, 0.2, 0.2, 0.2, 1.0)),
         IMAGE=dict(BBOX_NORMALIZE_MEANS=(0.0, 0.0, 0.0, 0.0), BBOX_NORMALIZE_STDS=(0.1, 0.1, 0.2, 0.2)))
     c.TEST = dict(SCALES=(1.0,), NMS_THRESH=0.6, BBOX_REG=True, HAS_RPN=True, RPN_NMS_THRESH=0.7,

@@ -81,6 +81,121 @@ class GradientBucket:
         return 0.0          # single process: mark_fault() raises at once, the slot is never written (and no host sync here)
 
 
+class FusedSGD(torch.optim.Optimizer):
+    """torch.optim.SGD(groups, momentum=...) of lib/model/train_val.py:207-208 as ONE kernel launch over the gradient
+    bucket (ops.sgd_update, csrc/optim.hip): clip, weight decay, momentum, step and the clearing of the gradients in one
+    pass.  Built from the same one-group-per-parameter list as the torch optimizer (``sgd_param_groups``), so ``scale_lr``
+    and every reader of ``param_groups`` work unchanged; the groups carry torch.optim.SGD's keys, the momentum buffers are
+    views into one flat buffer laid out like ``bucket.flat`` and appear as ``state[p]['momentum_buffer']``, so
+    ``state_dict()`` has torch.optim.SGD's layout and loads into one (and the reverse).  Dampening, Nesterov momentum and
+    ``maximize`` are not implemented (the reference uses none of them).  One exception to "torch's optimizer": with
+    ``momentum == 0`` torch keeps no buffer, while this one still computes b = b * 0 + d - the same value unless a buffer
+    word once became inf or NaN (it then stays NaN; the parameter is lost at that point on either path) - and
+    ``state_dict()`` carries ``momentum_buffer`` entries torch.optim.SGD(momentum=0) would not have.  An update is the
+    kernel launch plus a fill of the bucket's fault slot when the gradients are cleared.  No CPU path."""
+
+    def __init__(self, params, bucket, momentum=0.0):
+        defaults = dict(lr=cfg.TRAIN.LEARNING_RATE, momentum=momentum, dampening=0, weight_decay=0, nesterov=False,
+                        maximize=False, foreach=None, differentiable=False, fused=None)
+        super().__init__(params, defaults)
+        from .. import ops
+        self._ops = ops
+        self.bucket = bucket
+        self.momentum = float(momentum)
+        offsets, off = {}, 0
+        for p in bucket.params:
+            offsets[id(p)] = off
+            off += p.numel()
+        self._params = [p for g in self.param_groups for p in g['params']]
+        if len(set(id(p) for p in self._params)) != len(self._params) or any(id(p) not in offsets for p in self._params):
+            raise ValueError("FusedSGD: every parameter must be in the gradient bucket, once")
+        if any(len(g['params']) != 1 for g in self.param_groups):
+            raise ValueError("FusedSGD: one param group per parameter (sgd_param_groups)")
+        for i, p in enumerate(self._params):
+            # the segment table describes a parameter as numel() consecutive floats, element k next to gradient element k
+            if p.dtype != torch.float32 or p.device != bucket.flat.device or not p.is_contiguous():
+                raise ValueError("FusedSGD: parameter %d %s must be contiguous float32 on %s (got %s, %s, contiguous=%s)"
+                                 % (i, tuple(p.shape), bucket.flat.device, p.dtype, p.device, p.is_contiguous()))
+        self.momentum_flat = torch.zeros_like(bucket.flat)
+        self._offsets = [offsets[id(p)] for p in self._params]
+        for p, o in zip(self._params, self._offsets):
+            self.state[p]['momentum_buffer'] = self.momentum_flat[o:o + p.numel()].view_as(p)
+        dev = bucket.flat.device
+        lrs, wds = self._rates()
+        self._seg_host, chunks = ops.sgd_tables([p.data_ptr() for p in self._params], self._offsets,
+                                                [p.numel() for p in self._params], lrs, wds)
+        self._grad_ptrs = [bucket.flat.data_ptr() + 4 * o for o in self._offsets]
+        self._seg_dev = torch.empty(self._seg_host.nbytes, dtype=torch.uint8, device=dev)
+        self._chunks_dev = torch.from_numpy(chunks).to(dev)
+        self._upload()
+        self.uploads = 1              # how often the segment table went to the device (the tests read it)
+
+    def _rates(self):
+        lrs = np.array([g['lr'] for g in self.param_groups], dtype=np.float32)
+        wds = np.array([g['weight_decay'] for g in self.param_groups], dtype=np.float32)
+        return lrs, wds
+
+    def _upload(self):
+        self._seg_dev.copy_(torch.from_numpy(self._seg_host.view(np.uint8).copy()))
+
+    def _check(self):
+        """Nothing is updated unless the tables still describe the parameters and their gradients."""
+        for i, (p, g) in enumerate(zip(self._params, self.param_groups)):
+            if p.data_ptr() != int(self._seg_host['param'][i]) or not p.is_contiguous():
+                raise RuntimeError("FusedSGD: the storage of parameter %d %s was replaced after the optimizer was built "
+                                   "(assign with copy_(), not .data = ...): nothing was updated" % (i, tuple(p.shape)))
+            grad = p.grad
+            if grad is None or grad.data_ptr() != self._grad_ptrs[i]:
+                raise RuntimeError("FusedSGD: .grad of parameter %d %s is no longer the gradient bucket's view (zero the "
+                                   "gradients in place, zero_grad(set_to_none=False)): nothing was updated"
+                                   % (i, tuple(p.shape)))
+            if g['momentum'] != self.momentum or g['dampening'] or g['nesterov'] or g['maximize']:
+                raise RuntimeError("FusedSGD: group %d asks for momentum %r, dampening %r, nesterov %r, maximize %r; one "
+                                   "momentum (%r) and none of the others are implemented: nothing was updated"
+                                   % (i, g['momentum'], g['dampening'], g['nesterov'], g['maximize'], self.momentum))
+
+    @torch.no_grad()
+    def fused_update(self, clip=0.0, zero=False):
+        """One launch: clamp the gradients to +-``clip`` (<= 0 or inf: no clip), step, and with ``zero`` leave every
+        gradient word +0.0 (the bucket's fault slot included)."""
+        self._check()
+        lrs, wds = self._rates()
+        if not (np.array_equal(lrs, self._seg_host['lr']) and np.array_equal(wds, self._seg_host['weight_decay'])):
+            self._seg_host['lr'], self._seg_host['weight_decay'] = lrs, wds
+            self._upload()
+            self.uploads += 1
+        self._ops.sgd_update(self.bucket.flat, self.momentum_flat, self._seg_host, self._seg_dev, self._chunks_dev,
+                             self.momentum, clip=clip, zero_grads=zero)
+        if zero:
+            self.bucket.fault.zero_()         # the slot behind the gradients is no segment
+        # the kernel wrote through raw pointers: the caches of weight-derived tensors are keyed by the version counters
+        torch.autograd.graph.increment_version(self._params)
+
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.fused_update(clip=0.0, zero=False)
+        return loss
+
+    def zero_grad(self, set_to_none=False):
+        self.bucket.zero()
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.SGD's layout; the momentum buffers are copied INTO the views of the flat buffer."""
+        super().load_state_dict(state_dict)
+        with torch.no_grad():
+            for p, o in zip(self._params, self._offsets):
+                view = self.momentum_flat[o:o + p.numel()].view_as(p)
+                loaded = self.state.get(p, {}).get('momentum_buffer')
+                if loaded is None:
+                    view.zero_()
+                elif loaded.data_ptr() != view.data_ptr():
+                    view.copy_(loaded)
+                self.state[p] = {'momentum_buffer': view}
+
+
 class DataParallelOptimizer:
     """The optimizer object handed to ``Network.train_step(blobs, optimizer, update_weights)``: ``step()`` first
     averages the flat gradient bucket over the ranks, ``zero_grad()`` clears the bucket in place (the views stay)."""
@@ -91,6 +206,8 @@ class DataParallelOptimizer:
         self.group = group
         self._reduced = False
         self._fault_text = None
+        if hasattr(optimizer, 'fused_update'):
+            self.fused_update = self._fused_update
 
     @property
     def param_groups(self):
@@ -138,6 +255,13 @@ class DataParallelOptimizer:
 
     def zero_grad(self, set_to_none=False):
         self.bucket.zero()
+        self._reduced = False
+
+    def _fused_update(self, clip=0.0, zero=False):
+        """``fused_update`` of a FusedSGD inside (the attribute exists only then): average over the ranks (a no-op when the
+        caller already did, as Network.apply_update does), then the launch that clips, steps and clears."""
+        self.reduce()
+        self.optimizer.fused_update(clip=clip, zero=zero)
         self._reduced = False
 
     def state_dict(self):
@@ -193,8 +317,13 @@ class SolverWrapper:
         self.net.to(self.net._device)
         if self.data_parallel:
             broadcast_parameters(self.net)
-        sgd = torch.optim.SGD(sgd_param_groups(self.net), momentum=cfg.TRAIN.MOMENTUM)
-        self.bucket = GradientBucket([p for g in sgd.param_groups for p in g['params']])
+        groups = sgd_param_groups(self.net)
+        self.bucket = GradientBucket([p for g in groups for p in g['params']])
+        if cfg.TRAIN.get('FUSED_UPDATE', False):
+            # the whole update as one HIP launch over the bucket (default off: profiles/fused_update.md)
+            sgd = FusedSGD(groups, self.bucket, momentum=cfg.TRAIN.MOMENTUM)
+        else:
+            sgd = torch.optim.SGD(groups, momentum=cfg.TRAIN.MOMENTUM)
         self.optimizer = DataParallelOptimizer(sgd, self.bucket)
         return cfg.TRAIN.LEARNING_RATE, self.optimizer
 

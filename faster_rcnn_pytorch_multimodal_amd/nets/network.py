@@ -724,6 +724,18 @@ class Network(nn.Module):
         train_step): data-parallel average, per-element gradient clip, optimizer step, gradients cleared.  ``in_place``:
         captured training graphs accumulate into the gradient buffers and read the derived filters by ADDRESS, so the
         gradients are zeroed in place and the filters re-derived in place."""
+        if hasattr(optimizer, 'fused_update'):
+            # cfg.TRAIN.FUSED_UPDATE (model/train_val.FusedSGD): clip, step and clearing are one kernel over the gradient
+            # bucket (plus a fill of the bucket's fault slot), in the same order - average over the ranks first, then clip,
+            # then step.  DataParallelOptimizer.fused_update reduces by itself (once per update: a second call is a no-op);
+            # the call here keeps the order explicit for any other optimizer that offers reduce() and fused_update()
+            if hasattr(optimizer, 'reduce'):
+                optimizer.reduce()
+            optimizer.fused_update(clip=float(cfg.GRAD_MAX_CLIP), zero=True)
+            if in_place:
+                from ..model.train_graph import after_optimizer_step
+                after_optimizer_step(self)
+            return
         if hasattr(optimizer, 'reduce'):
             optimizer.reduce()        # data parallel: average over the ranks first, clip the batch gradient after
         self._clip_gradients()

@@ -1545,3 +1545,57 @@ def spatial_mean_bwd(dout, pooled):
     dx = torch.empty((r, pooled, pooled, c), dtype=torch.float32, device=dout.device)
     _hip.check(lib.frcnn_spatial_mean_bwd(_ptr(dout), _ptr(dx), r, pooled, c, _stream()), "frcnn_spatial_mean_bwd")
     return dx
+
+
+# frcnn_sgd_update: elements per workgroup and the 32-byte row of the segment table (include/frcnn_hip.h frcnn_sgd_segment)
+SGD_CHUNK = 4096
+
+
+def sgd_segment_dtype():
+    import numpy as np
+    return np.dtype([('param', '<u8'), ('offset', '<i8'), ('count', '<i8'), ('lr', '<f4'), ('weight_decay', '<f4')])
+
+
+def sgd_tables(param_ptrs, offsets, counts, lrs, weight_decays):
+    """Host tables of ``sgd_update``: the segment table (one ``sgd_segment_dtype`` row per parameter) and the chunk table
+    (int32 (num_chunks, 2): segment, chunk index; ceil(count / SGD_CHUNK) rows per segment)."""
+    import numpy as np
+    seg = np.zeros(len(param_ptrs), dtype=sgd_segment_dtype())
+    seg['param'], seg['offset'], seg['count'] = param_ptrs, offsets, counts
+    seg['lr'], seg['weight_decay'] = lrs, weight_decays
+    per = (seg['count'] + SGD_CHUNK - 1) // SGD_CHUNK
+    chunks = np.empty((int(per.sum()), 2), dtype=np.int32)
+    chunks[:, 0] = np.repeat(np.arange(len(seg), dtype=np.int32), per)
+    chunks[:, 1] = np.concatenate([np.arange(n, dtype=np.int32) for n in per] or [np.zeros(0, np.int32)])
+    return seg, chunks
+
+
+def sgd_update(grad_flat, momentum_flat, segments_host, segments_dev, chunks_dev, momentum, clip=0.0, zero_grads=False):
+    """The solver's weight update for all parameters in one launch (frcnn_sgd_update; lib/model/train_val.py:207-208,
+    379-382): per element g = clamp(g, -clip, clip); d = g + wd * p; b = b * momentum + d; p = p - lr * b; g = 0 when
+    ``zero_grads``.  ``grad_flat`` / ``momentum_flat``: flat fp32 device buffers of one layout; ``segments_host``: the numpy
+    segment table of ``sgd_tables``, ``segments_dev`` its copy on the device as uint8 (the caller keeps them equal: the
+    arguments are checked on the host copy), ``chunks_dev``: the chunk table on the device, int32 (num_chunks, 2).
+    ``clip`` <= 0 or inf: no clip.  The parameters are written through the pointers in the table: the caller bumps their
+    version counters."""
+    lib = _hip.load()
+    _dev_f32(grad_flat, "sgd_update: grad_flat")
+    _dev_f32(momentum_flat, "sgd_update: momentum_flat")
+    if grad_flat.dim() != 1 or momentum_flat.shape != grad_flat.shape or momentum_flat.device != grad_flat.device:
+        raise _hip.HipError("sgd_update: grad_flat and momentum_flat must be flat buffers of one size on one device")
+    if segments_host.dtype != sgd_segment_dtype() or segments_host.ndim != 1 or not segments_host.flags['C_CONTIGUOUS']:
+        raise _hip.HipError("sgd_update: segments_host must be a contiguous 1-d array of sgd_segment_dtype()")
+    num = int(segments_host.shape[0])
+    for t, name, dtype, count in ((segments_dev, "segments_dev", torch.uint8, num * 32),
+                                  (chunks_dev, "chunks_dev", torch.int32, None)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != grad_flat.device:
+            raise _hip.HipError("sgd_update: %s must be a tensor on the MI355X (got %s); this package has no CPU path"
+                                % (name, getattr(t, "device", type(t))))
+        if t.dtype != dtype or not t.is_contiguous() or (count is not None and t.numel() != count):
+            raise _hip.HipError("sgd_update: %s must be contiguous %s%s" % (name, dtype, "" if count is None else " of %d bytes" % count))
+    if chunks_dev.dim() != 2 or chunks_dev.shape[1] != 2:
+        raise _hip.HipError("sgd_update: chunks_dev must have shape (num_chunks, 2), got %s" % (tuple(chunks_dev.shape),))
+    _hip.check(lib.frcnn_sgd_update(_ptr(grad_flat), _ptr(momentum_flat), grad_flat.numel(),
+                                    _ptr(segments_dev) if num else None, segments_host.ctypes.data if num else None, num,
+                                    _ptr(chunks_dev) if chunks_dev.numel() else None, int(chunks_dev.shape[0]),
+                                    float(momentum), float(clip), int(bool(zero_grads)), _stream()), "frcnn_sgd_update")

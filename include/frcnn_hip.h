@@ -761,6 +761,40 @@ int frcnn_filter_per_class_lidar(const float* pred_boxes, const float* cls_prob,
                                  int max_out, float* dets, int* det_count, int* det_roi, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The solver's weight update (lib/model/train_val.py:207-208 torch.optim.SGD(params, momentum=cfg.TRAIN.MOMENTUM) with one
+ * param group per parameter, :379-382 the step that ends a pseudo batch; version 114): gradient clip, weight decay,
+ * momentum, step and the clearing of the gradients for ALL trainable parameters of a network in ONE launch.
+ *   grad_flat, momentum_flat   two flat fp32 device buffers of flat_elems elements with the same layout (the gradients of
+ *                              model/train_val.GradientBucket and the momentum buffers next to them); they must not overlap;
+ *   segments_dev               device table, one row per parameter: where the parameter lives, where its gradient /
+ *                              momentum start in the flat buffers (in elements), how many elements, its learning rate and
+ *                              weight decay.  segments_host is a HOST copy of the same rows: every argument check is made
+ *                              on it, without a host synchronisation (the caller keeps the two equal);
+ *   chunks_dev                 device table of num_chunks (segment, chunk) int pairs: workgroup i updates elements
+ *                              chunk * FRCNN_SGD_CHUNK .. of that segment.  Every segment contributes
+ *                              ceil(count / FRCNN_SGD_CHUNK) rows, in any order; num_chunks is checked against that sum;
+ *   momentum                   torch.optim.SGD's momentum (dampening 0, no Nesterov); the momentum buffers start at zero;
+ *   clip                       per-element clamp of the gradient to [-clip, +clip] first; <= 0 or +inf: no clip;
+ *   zero_grads                 1: every gradient word is left as +0.0; 0: the (clipped) gradient is left in place.
+ * Per element, torch's operations in torch's order, each rounded once (no fma):
+ *   g = clamp(g, -clip, clip) (NaN stays NaN);  d = g + wd * p (skipped when wd == 0);  b = b * momentum + d;
+ *   p = p + (-lr) * b.
+ * Segments may start at any element offset and parameters at any float-aligned address.  Zero segments: nothing is
+ * launched, returns FRCNN_OK.  Every kernel argument is a pointer or a launch-invariant scalar (learning rates and weight
+ * decays live in the device table).  No allocation, no host synchronisation, one kernel launch. */
+#define FRCNN_SGD_CHUNK 4096
+typedef struct frcnn_sgd_segment {
+  float* param;        /* device pointer of the parameter's first element */
+  int64_t offset;      /* first element of its gradient / momentum in the flat buffers */
+  int64_t count;       /* elements */
+  float lr;
+  float weight_decay;
+} frcnn_sgd_segment;
+int frcnn_sgd_update(float* grad_flat, float* momentum_flat, int64_t flat_elems, const frcnn_sgd_segment* segments_dev,
+                     const frcnn_sgd_segment* segments_host, int num_segments, const int* chunks_dev, int64_t num_chunks,
+                     float momentum, float clip, int zero_grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
