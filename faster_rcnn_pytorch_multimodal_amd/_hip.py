@@ -81,6 +81,11 @@ PROTOTYPES = {
     "frcnn_filter_set_variant": (c_int, [c_int]),
     "frcnn_filter_per_class_lidar": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_int, c_int, _P, _P, _P, _P,
                                              c_size_t, _P]),
+    "frcnn_nms_rotated_ws_bytes": (c_size_t, [c_int]),
+    "frcnn_nms_rotated": (c_int, [_P, _P, c_int, c_float, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "frcnn_filter_per_class_lidar_rot_ws_bytes": (c_size_t, [c_int, c_int]),
+    "frcnn_filter_per_class_lidar_rot": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_int, c_int, _P, _P, _P, _P,
+                                                 c_size_t, _P]),
     "frcnn_act_bwd": (c_int, [_P, _P, _P, c_int, c_int64, c_int, _P, _P, _P]),
     "frcnn_bev_voxelize_grid": (c_int, [POINTER(c_float), POINTER(c_float), POINTER(c_int)]),
     "frcnn_bev_voxelize_ws_bytes": (c_size_t, [c_int, POINTER(c_float), POINTER(c_float), c_int]),

@@ -34,6 +34,7 @@ SOURCES = {
     "image_augment.hip": ["-ffp-contract=off"],
     "eval_match.hip": ["-ffp-contract=off"],
     "optim.hip": ["-ffp-contract=off"],
+    "nms_rotated.hip": ["-ffp-contract=off"],
 }
 COMMON_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

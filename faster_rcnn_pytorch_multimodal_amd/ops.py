@@ -624,6 +624,27 @@ def nms_sorted(boxes, thresh, max_keep=None, n_dev=None, want_mask=False):
     return keep_idx, keep_count, keep_mask
 
 
+def nms_rotated(boxes, thresh, n=None, max_keep=None):
+    """Rotated BEV NMS over 7-DoF boxes (n_max, 7) [xc,yc,zc,l,w,h,ry] already in descending-score order
+    (frcnn_nms_rotated; the float64 rule of utils/bbox.nms_rotated_host).  ``n``: device int32 tensor holding the live count
+    (None: every row).  Returns (keep_idx int64 (max_keep,), keep_count int32 (1,)); entries past the count are 0."""
+    lib = _hip.load()
+    _dev_f32(boxes, "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 7 or boxes.shape[0] == 0:
+        raise _hip.HipError("nms_rotated: boxes must be (N>0, 7), got %s" % (tuple(boxes.shape),))
+    if n is not None and not (isinstance(n, torch.Tensor) and n.is_cuda and n.dtype == torch.int32):
+        raise _hip.HipError("nms_rotated: n must be a device int32 tensor (the live count is read on the device)")
+    n_max = boxes.shape[0]
+    max_keep = n_max if max_keep is None or max_keep <= 0 else min(int(max_keep), n_max)
+    keep_idx = torch.empty((max_keep,), dtype=torch.int64, device=boxes.device)     # the kernel zeroes the unused tail
+    keep_count = torch.empty((1,), dtype=torch.int32, device=boxes.device)
+    ws_bytes = lib.frcnn_nms_rotated_ws_bytes(n_max)
+    ws = _workspace(ws_bytes, boxes.device)
+    _hip.check(lib.frcnn_nms_rotated(_ptr(boxes), _ptr(n), n_max, float(thresh), max_keep, _ptr(keep_idx), None,
+                                     _ptr(keep_count), _ptr(ws), ws_bytes, _stream()), "frcnn_nms_rotated")
+    return keep_idx, keep_count
+
+
 def make_rois(sorted_boxes, sorted_scores, keep_idx, keep_count):
     lib = _hip.load()
     m = keep_idx.numel()
@@ -737,9 +758,10 @@ def generate_anchors_3d(base, height, width, feat_stride):
 
 
 def filter_per_class_lidar(pred_boxes, cls_prob, thresh, nms_thresh, max_dets, max_out=None, roi_count=None,
-                           want_rois=False):
+                           want_rois=False, rotated=False):
     """7-DoF form: returns (dets (K, max_out, 8) [xc,yc,zc,l,w,h,ry,score], det_count int32 (K,)[, det_roi int32
-    (K, max_out)])."""
+    (K, max_out)]).  ``rotated``: suppress on the rotated BEV footprints (frcnn_filter_per_class_lidar_rot, the rule of
+    utils/bbox.nms_rotated_host) instead of the reference's yaw-less rectangles; same outputs, same shapes."""
     lib = _hip.load()
     _dev_f32(pred_boxes, "pred_boxes"); _dev_f32(cls_prob, "cls_prob")
     r, k = cls_prob.shape
@@ -748,13 +770,13 @@ def filter_per_class_lidar(pred_boxes, cls_prob, thresh, nms_thresh, max_dets, m
     max_out = r if max_out is None else max_out
     dets = torch.empty((k, max_out, 8), dtype=torch.float32, device=cls_prob.device)    # every row is written by the call
     det_count = torch.empty((k,), dtype=torch.int32, device=cls_prob.device)
-    ws_bytes = lib.frcnn_filter_per_class_ws_bytes(r, k)
+    name = "frcnn_filter_per_class_lidar_rot" if rotated else "frcnn_filter_per_class_lidar"
+    ws_bytes = (lib.frcnn_filter_per_class_lidar_rot_ws_bytes if rotated else lib.frcnn_filter_per_class_ws_bytes)(r, k)
     ws = _workspace(ws_bytes, cls_prob.device)
     det_roi = torch.empty((k, max_out), dtype=torch.int32, device=cls_prob.device) if want_rois else None   # -1 = no detection
-    _hip.check(lib.frcnn_filter_per_class_lidar(_ptr(pred_boxes), _ptr(cls_prob), _ptr(roi_count), r, k, float(thresh),
-                                                float(nms_thresh), int(max_dets), int(max_out), _ptr(dets),
-                                                _ptr(det_count), _ptr(det_roi), _ptr(ws), ws_bytes, _stream()),
-               "frcnn_filter_per_class_lidar")
+    _hip.check(getattr(lib, name)(_ptr(pred_boxes), _ptr(cls_prob), _ptr(roi_count), r, k, float(thresh),
+                                  float(nms_thresh), int(max_dets), int(max_out), _ptr(dets), _ptr(det_count),
+                                  _ptr(det_roi), _ptr(ws), ws_bytes, _stream()), name)
     return (dets, det_count, det_roi) if want_rois else (dets, det_count)
 
 

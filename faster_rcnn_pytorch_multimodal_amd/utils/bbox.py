@@ -50,3 +50,35 @@ def bbox_voxel_grid_to_pc(bboxes, bev_extents, info):
     """lib/utils/bbox.py:140-162, the inverse (host copy of the detections, lib/model/test.py:223-224)."""
     from ..model.test import bbox_voxel_grid_to_pc as impl
     return impl(bboxes, bev_extents, info)
+
+
+def nms_rotated_host(boxes, scores, thresh, at_equal=True):
+    """Rotated BEV NMS on the host in float64: what cfg.TEST.NMS_ROTATED means (not in the reference: the form its authors
+    left commented out at lib/utils/filter_predictions.py:56-57), and the rule the device entries frcnn_nms_rotated /
+    frcnn_filter_per_class_lidar_rot restate.
+
+    ``boxes`` (N, >=7) [xc,yc,zc,l,w,h,ry], ``scores`` (N,).  The boxes are visited by (score descending, index
+    ascending); a box is removed when a KEPT earlier box i has
+    ``waymo_eval.iou(bbgt=box_i[None], bb=box_j, 'bev')`` >= ``thresh`` (``at_equal``; the ``>`` of
+    ``ops.set_nms_suppress_at_equal(False)`` otherwise) - box j's footprint clipped against box i's; the two argument
+    orders differ in the last bits.  ``thresh`` is compared as the float32 the device entries receive, widened to float64.
+    A NaN overlap never suppresses.  ``thresh`` <= 0 is refused: disjoint boxes have IoU 0.  Returns the kept indices into
+    the input, in visiting order."""
+    from ..datasets.waymo_eval import iou
+    boxes = np.asarray(boxes, dtype=np.float64)
+    scores = np.asarray(scores)
+    if boxes.ndim != 2 or boxes.shape[1] < 7 or scores.shape != (boxes.shape[0],):
+        raise ValueError("nms_rotated_host: boxes (N, >=7) and scores (N,), got %s and %s" % (boxes.shape, scores.shape))
+    t = float(np.float32(thresh))
+    if not t > 0.0:
+        raise ValueError("nms_rotated_host: thresh %r must be > 0 (disjoint boxes have IoU 0)" % (thresh,))
+    order = np.lexsort((np.arange(boxes.shape[0]), -scores))      # score descending, index ascending
+    kept = []
+    with np.errstate(invalid='ignore', divide='ignore'):
+        for j in order:
+            if kept:
+                ov = iou(boxes[kept][:, :7], boxes[j, :7], 'bev')     # every kept predecessor against box j
+                if np.any(ov >= t) if at_equal else np.any(ov > t):
+                    continue
+            kept.append(int(j))
+    return np.asarray(kept, dtype=np.int64)

@@ -16,13 +16,16 @@ def filter_device(rois_count, cls_prob, pred_boxes, info, thresh=0.1, max_dets=0
                   uncertainties=None):
     """Asynchronous form: returns (dets (K, max_out, E+1+U), det_count (K,)) device tensors, E = 4 image /
     7 LiDAR.  Image ``pred_boxes`` are clamped IN PLACE like the reference (:85-91); LiDAR boxes are not clamped
-    and are suppressed on their yaw-less BEV rectangle (:55-62,67).  With a non-empty ``uncertainties`` dict
+    and are suppressed on their yaw-less BEV rectangle (:55-62,67) - or, with cfg.TEST.NMS_ROTATED (not in the reference:
+    the form its authors left commented out at :56-57), on their rotated footprints; the image detector never reads that
+    switch.  With a non-empty ``uncertainties`` dict
     (cfg.UC.*) every detection row is followed by its U uncertainty columns in the order of
     nets/uncertainty.UNCERTAINTY_ORDER (nms_hstack_var_torch :23-43 + stack_uncertainties, lib/model/test.py:260-270)."""
     want = bool(uncertainties)
     if db_type == 'lidar':
         out = ops.filter_per_class_lidar(pred_boxes, cls_prob, thresh, cfg.TEST.NMS_THRESH, max_dets, max_out,
-                                         roi_count=rois_count, want_rois=want)
+                                         roi_count=rois_count, want_rois=want,
+                                         rotated=bool(cfg.TEST.get('NMS_ROTATED', False)))
     else:
         info = np.asarray(info, dtype=np.float32)
         frame_w, frame_h, scale = info[1] - info[0], info[3] - info[2], info[6]

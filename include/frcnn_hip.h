@@ -762,6 +762,37 @@ int frcnn_filter_per_class_lidar(const float* pred_boxes, const float* cls_prob,
                                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Rotated BEV NMS (version 115, opt-in: cfg.TEST.NMS_ROTATED).  The reference suppresses LiDAR detections on the yaw-less
+ * rectangle (lib/utils/filter_predictions.py:55-67); its authors left the rotated form commented out at :56-57 ("Turned
+ * off auto rotating").  These entries are that form, stated exactly:
+ *   boxes are [xc,yc,zc,l,w,h,ry] float32 rows in (score descending, RoI index ascending) order, widened to float64;
+ *   for i < j  iou(i, j) = datasets/waymo_eval.iou(bbgt = box_i[None], bb = box_j, 'bev')  - box j's rotated footprint
+ *   clipped against box i's (the argument order is part of the contract), over l*w + l*w - intersection, in float64
+ *   with one rounding per operation;
+ *   box j is removed when a KEPT i < j has iou >= (double)thresh (frcnn_nms_set_suppress_at_equal(1), the default) or
+ *   iou > (double)thresh (0).  A NaN overlap never suppresses.
+ * thresh <= 0 (or NaN) is refused with FRCNN_ERR_ARG: disjoint boxes have IoU 0 and would suppress each other.
+ * Three kernel launches on `stream`, sized by n_max / num_rois; the live counts are read on the device; no host
+ * synchronisation, no memset / memcpy nodes: the calls capture into a hipGraph.
+ *
+ * frcnn_nms_rotated: boxes7 (n_max, 7) already in descending score order, n_dev (device int, may be NULL -> n_max) live.
+ * Outputs as frcnn_nms: keep_idx[max_keep] int64 positions of the survivors in score order (entries past keep_count are
+ * written as 0), keep_mask[n_max] bytes (may be NULL; 1 for the survivors counted in keep_count), keep_count[0] =
+ * min(#survivors, max_keep).  n_max <= 4096, larger is FRCNN_ERR_ARG. */
+size_t frcnn_nms_rotated_ws_bytes(int n_max);
+int frcnn_nms_rotated(const float* boxes7, const int* n_dev, int n_max, float thresh, int max_keep, int64_t* keep_idx,
+                      uint8_t* keep_mask, int* keep_count, void* ws, size_t ws_bytes, void* stream);
+
+/* frcnn_filter_per_class_lidar with the rotated rule in place of filter_predictions.py:55-67's yaw-less one (the
+ * commented-out :56-57): same arguments, same outputs - score threshold, order, the max_dets cut with ties
+ * (lib/model/test.py:213-221), zero rows past det_count, det_roi -1 there, empty class 0, boxes not clamped.
+ * num_rois <= 1024 (the reference uses 300), larger is FRCNN_ERR_ARG.  Workspace: frcnn_filter_per_class_lidar_rot_ws_bytes. */
+size_t frcnn_filter_per_class_lidar_rot_ws_bytes(int num_rois, int num_classes);
+int frcnn_filter_per_class_lidar_rot(const float* pred_boxes, const float* cls_prob, const int* roi_count, int num_rois,
+                                     int num_classes, float thresh, float nms_thresh, int max_dets, int max_out,
+                                     float* dets, int* det_count, int* det_roi, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The solver's weight update (lib/model/train_val.py:207-208 torch.optim.SGD(params, momentum=cfg.TRAIN.MOMENTUM) with one
  * param group per parameter, :379-382 the step that ends a pseudo batch; version 114): gradient clip, weight decay,
  * momentum, step and the clearing of the gradients for ALL trainable parameters of a network in ONE launch.
