@@ -100,6 +100,8 @@ PROTOTYPES = {
     "frcnn_image_augment_ws_bytes": (c_size_t, [c_int, c_int]),
     "frcnn_image_augment": (c_int, [_P, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_float), c_uint32, _P, _P, c_size_t,
                                     _P, _P, _P]),
+    "frcnn_image_spatter": (c_int, [_P, c_int, c_int, POINTER(c_float), POINTER(c_float), c_int, POINTER(c_float), c_int,
+                                    c_uint32, _P, _P, _P, _P, _P]),
     "frcnn_eval_match_ws_bytes": (c_size_t, [c_int, c_int]),
     "frcnn_eval_match": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_double, c_double,
                                  c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),

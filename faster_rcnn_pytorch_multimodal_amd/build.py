@@ -32,6 +32,7 @@ SOURCES = {
     "voxelize.hip": ["-ffp-contract=off"],
     "lidar_augment.hip": ["-ffp-contract=off"],
     "image_augment.hip": ["-ffp-contract=off"],
+    "image_spatter.hip": ["-ffp-contract=off"],
     "eval_match.hip": ["-ffp-contract=off"],
     "optim.hip": ["-ffp-contract=off"],
     "nms_rotated.hip": ["-ffp-contract=off"],

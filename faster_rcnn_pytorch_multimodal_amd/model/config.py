@@ -104,7 +104,11 @@ def _defaults():
                    # roi_data_layer/image_augment.py).  EN_AUG is the master switch: while it is False, augment_en=True
                    # raises for image frames as before; the per-step switches follow cfg.LIDAR.EN_AUG_*
                    EN_AUG=False, EN_AUG_FLIP=True, EN_AUG_FILTER=True, EN_AUG_NOISE=True, EN_AUG_HUE_SAT=True,
-                   EN_AUG_AFFINE=True, EN_AUG_DROPOUT=True)
+                   EN_AUG_AFFINE=True, EN_AUG_DROPOUT=True,
+                   # not in the reference: the test-time Spatter corruption of cfg.TEST.AUGMENT_EN (minibatch.py:648-664)
+                   # on the device (frcnn_image_spatter).  While EN_TEST_SPATTER is False, augment_en=True with
+                   # mode='test' raises as before; the reference's severity is 5 (4 is the other one of the mud branch)
+                   EN_TEST_SPATTER=False, TEST_SPATTER_SEVERITY=5)
     # sensor range in metres, read by the rain simulation as cfg[cfg.DB_NAME.upper()].LIDAR_MAX_RANGE (config.py:431-449)
     c.WAYMO = dict(LIDAR_MAX_RANGE=200)
     # IMG_SIZE [height, width] of the front camera: the frame of the field-of-view filter (config.py:442,447)

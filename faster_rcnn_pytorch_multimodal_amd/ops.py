@@ -829,8 +829,9 @@ AUG_GAUSS, AUG_DROPOUT, AUG_ROTATE, AUG_SWAP_XY, AUG_FLIP_Y, AUG_FLIP_X, AUG_RAI
 # counter-based draws of the kernel (csrc/rng.h): normal01 streams of the distortion (x, y, z) and of the rain shift,
 # uniform01 streams of the two keep masks
 # frcnn_image_augment: normal01 streams of the additive noise (one per channel), uniform01 stream of the pixel dropout
+# frcnn_image_spatter: normal01 stream of the liquid field (reads the uniform streams 88 and 89)
 AUG_STREAM = {'gauss_x': 32, 'gauss_y': 33, 'gauss_z': 34, 'rain': 35, 'dropout': 72, 'test_dropout': 73,
-              'image_noise_0': 40, 'image_noise_1': 41, 'image_noise_2': 42, 'image_dropout': 86}
+              'image_noise_0': 40, 'image_noise_1': 41, 'image_noise_2': 42, 'image_dropout': 86, 'image_spatter': 44}
 
 
 def _fov_arguments(proj, img_size):
@@ -990,6 +991,42 @@ def image_augment(img, aug, out=None, scratch=None, seed_dev=None, debug_pre=Non
                                        int(aug.seed) & 0xFFFFFFFF, _seed_dev(seed_dev), _ptr(scratch),
                                        0 if scratch is None else scratch.numel(), _ptr(out), _ptr(debug_pre), _stream()),
                "frcnn_image_augment")
+    return out
+
+
+# frcnn_image_spatter: what the kernel's halo holds (include/frcnn_hip.h FRCNN_SPATTER_MAX_TAPS*)
+SPATTER_MAX_TAPS = (9, 13)
+
+
+def image_spatter(img, spatter, out=None, seed_dev=None, debug_liquid=None, debug_mask=None):
+    """Test-time Spatter corruption in front of ``prep_im_for_blob`` (frcnn_image_spatter; lib/roi_data_layer/minibatch.py:
+    648-664).  ``img``: uint8 (H, W, 3) device tensor in cv2.imread order; ``spatter``: the record
+    (``roi_data_layer.image_augment.Spatter`` or any object with ``severity`` and ``seed``; severities 1-3 raise
+    NotImplementedError).  Returns the corrupted uint8 frame (``out`` or a new tensor; ``out`` must not be ``img``).
+    ``debug_liquid`` / ``debug_mask``: float32 (H, W) device tensors receiving the field after the first blur and the mask
+    before its 0.8 cut (tests)."""
+    from .roi_data_layer.image_augment import spatter_params, spatter_taps
+    params = spatter_params(int(spatter.severity))
+    lib = _hip.load()
+    if not isinstance(img, torch.Tensor) or not img.is_cuda:
+        raise _hip.HipError("image_spatter: img must be a tensor on the MI355X (got %s); this package has no CPU path"
+                            % (getattr(img, "device", type(img)),))
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
+        raise _hip.HipError("image_spatter: img must be a contiguous uint8 (H, W, 3) frame, got %s %s"
+                            % (img.dtype, tuple(img.shape)))
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if out is None:
+        out = torch.empty_like(img)
+    elif out.dtype != torch.uint8 or out.shape != img.shape or not out.is_cuda or not out.is_contiguous():
+        raise _hip.HipError("image_spatter: out must be a contiguous uint8 device tensor of shape %s" % (tuple(img.shape),))
+    for name, dbg in (("debug_liquid", debug_liquid), ("debug_mask", debug_mask)):
+        if dbg is not None and _dev_f32(dbg, name).numel() != h * w:
+            raise _hip.HipError("image_spatter: %s must hold H*W floats" % name)
+    taps1, taps2 = spatter_taps(params[2]), spatter_taps(params[4])
+    _hip.check(lib.frcnn_image_spatter(_ptr(img), h, w, _hip.float_array(params), _hip.float_array(taps1), len(taps1),
+                                       _hip.float_array(taps2), len(taps2), int(spatter.seed) & 0xFFFFFFFF,
+                                       _seed_dev(seed_dev), _ptr(out), _ptr(debug_liquid), _ptr(debug_mask), _stream()),
+               "frcnn_image_spatter")
     return out
 
 

@@ -11,8 +11,15 @@ frame is a pure function of its record.
 Pinned by the reference's text: the decision tree, the probabilities and the parameter intervals below, the flip's box
 formula and the ignore rules.  The pixel operators themselves restate imgaug / cv2 / scikit-image, which are not
 available to this project: parity unpinned (``csrc/image_augment.hip`` lists the conventions).
+
+Test time (:648-664, cfg.TEST.AUGMENT_EN): the reference runs ``iaa.imgcorruptlike.Spatter(severity=5)`` over the frame.
+Behind cfg.IMAGE.EN_TEST_SPATTER the same split holds: ``draw_test_corruption`` makes the ``Spatter`` record (severity and
+the seed of the per-pixel draws) on the host, ``ops.image_spatter`` (``frcnn_image_spatter``, one fused launch) makes the
+pixels.  The operator's constants are restated from the published ImageNet-C code: parity unpinned
+(``csrc/image_spatter.hip``).
 """
 import math
+import zlib
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -34,6 +41,11 @@ NOISE_SCALE_RANGE = (0.0, 0.1 * 255)                              # :574
 HUE_SAT_RANGE = (-5, 5)                                           # :576, integers, hue and saturation drawn independently
 AFFINE_SCALE_RANGE, AFFINE_TRANSLATE_RANGE, AFFINE_SHEAR_RANGE = (0.9, 1.2), (-0.05, 0.05), (-0.05, 0.05)   # :580-584
 DROPOUT_P_RANGE, P_DROPOUT_PER_CHANNEL = (0.01, 0.05), 0.5        # :587
+# ImageNet-C spatter, mud branch: severity -> (loc, scale, sigma1, thr, sigma2).  PARITY UNPINNED (restated from the
+# published code); severities 1-3 are the water branch (Canny edges, distance transform), which is not built
+SPATTER_PARAMS = {4: (0.65, 0.3, 1.0, 0.65, 1.5), 5: (0.67, 0.4, 1.0, 0.65, 1.5)}
+SPATTER_MUD_COLOUR = (63 / 255.0, 42 / 255.0, 20 / 255.0)         # on memory channels 0, 1, 2 (csrc/image_spatter.hip)
+SPATTER_MASK_CUT = 0.8
 
 
 @dataclass(frozen=True)
@@ -81,6 +93,52 @@ class ImageAugment:
     @property
     def identity(self):
         return not (self.flip or self.active_stages or self.affine is not None or self.dropout is not None)
+
+
+@dataclass(frozen=True)
+class Spatter:
+    """The test-time corruption of one frame (:653): ``severity`` of ``iaa.imgcorruptlike.Spatter`` (4 or 5) and the
+    ``seed`` of the per-pixel draws on the device.  A frame is a pure function of (pixels, severity, seed)."""
+    severity: int = 5
+    seed: int = 0
+
+
+def spatter_params(severity):
+    """``(loc, scale, sigma1, thr, sigma2)`` of a severity.  1-3 are the water branch of the published operator: refused."""
+    if severity in (1, 2, 3):
+        raise NotImplementedError("Spatter severity %d is the water branch of the published operator (Canny edges, distance "
+                                  "transform), which is not built; severities 4 and 5 (mud) are" % severity)
+    if severity not in SPATTER_PARAMS:
+        raise ValueError("Spatter severity must be 4 or 5 (1-3 are not built), got %r" % (severity,))
+    return SPATTER_PARAMS[severity]
+
+
+def spatter_taps(sigma):
+    """Normalised taps of scikit-image / scipy's Gaussian as float32, computed in double: radius int(4 sigma + 0.5)
+    (9 taps for sigma 1, 13 for sigma 1.5), exp(-x^2 / 2 sigma^2)."""
+    radius = int(4.0 * float(sigma) + 0.5)
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    taps = np.exp(-(x * x) / (2.0 * float(sigma) ** 2))
+    return (taps / taps.sum()).astype(np.float32)
+
+
+def draw_test_corruption(rng=None, key=None):
+    """The ``Spatter`` record of one test frame: cfg.IMAGE.TEST_SPATTER_SEVERITY and a seed.  ``rng``: a
+    ``numpy.random.Generator``; None = the one given to ``set_augmentation_rng``.  Without either, the seed is
+    crc32(``key``) continued from cfg.RNG_SEED - ``key`` names the frame (its file) - so a frame's corruption depends on
+    the frame and the run's seed alone, not on the order or the rank it is visited in; without a key too, fresh OS entropy
+    as everywhere in this module."""
+    severity = int(cfg.IMAGE.TEST_SPATTER_SEVERITY)
+    spatter_params(severity)
+    if rng is None:
+        rng = _shared._RNG
+    if rng is not None:
+        seed = int(rng.integers(0, 1 << 32))
+    elif key is not None:
+        seed = zlib.crc32(str(key).encode('utf-8'), int(cfg.RNG_SEED) & 0xFFFFFFFF) & 0xFFFFFFFF
+    else:
+        seed = int(np.random.default_rng().integers(0, 1 << 32))
+    return Spatter(severity=severity, seed=seed)
 
 
 def gaussian_taps(sigma):

@@ -17,8 +17,9 @@ as the first step of the same per-point pass (``frcnn_lidar_augment_fov``).
 Image frames: with ``cfg.IMAGE.EN_AUG`` on, ``augment_en=True`` draws the reference's flip / blur-sharpen / noise /
 hue-saturation / affine / dropout per frame (``roi_data_layer/image_augment.py``, minibatch.py:540-647), runs the pixels
 through ``frcnn_image_augment`` on the device in front of ``frcnn_prep_image`` and moves, clips and flags the gt boxes on
-the host.  The switch defaults to off: ``augment_en=True`` then raises for images, as does the test-time ``Spatter``
-corruption (:648-664) always.
+the host.  The switch defaults to off: ``augment_en=True`` then raises for images.  The test-time ``Spatter`` corruption
+(:648-664, ``augment_en=True`` with ``mode='test'``: what cfg.TEST.AUGMENT_EN asks for) is behind ``cfg.IMAGE.EN_TEST_SPATTER``
+in the same way: on, the frame goes through ``frcnn_image_spatter`` on the device in front of ``frcnn_prep_image``; off, it raises.
 """
 import numpy as np
 import torch
@@ -88,8 +89,11 @@ def read_point_cloud_file(filename):
 
 def _no_augmentation(augment_en, mode='train'):
     if augment_en and mode == 'test':
-        raise NotImplementedError("augment_en=True with mode='test': the imgcorruptlike Spatter corruption of "
-                                  "lib/roi_data_layer/minibatch.py:648-664 is out of scope; pass augment_en=False")
+        if not cfg.IMAGE.EN_TEST_SPATTER:
+            raise NotImplementedError("augment_en=True with mode='test': the imgcorruptlike Spatter corruption of "
+                                      "lib/roi_data_layer/minibatch.py:648-664 is behind cfg.IMAGE.EN_TEST_SPATTER, which "
+                                      "is False; set it or pass augment_en=False")
+        return
     if augment_en and not cfg.IMAGE.EN_AUG:
         raise NotImplementedError("augment_en=True: image augmentation (lib/roi_data_layer/minibatch.py:540-647, "
                                   "roi_data_layer/image_augment.py) is behind cfg.IMAGE.EN_AUG, which is False; set it "
@@ -100,7 +104,9 @@ def _get_image_blob(roidb, im_scale, augment_en=False, mode='train', device='cud
     """minibatch.py:518-676.  ``roidb``: list with ONE filename (mode 'test') or ONE roidb entry (dict with 'filename').
     Returns (im_infos, blob (1, H', W', 3) float32 device tensor, local_roidb).  ``augment_en`` (train / val mode, behind
     cfg.IMAGE.EN_AUG): file -> uint8 frame on the device -> ``frcnn_image_augment`` (skipped for an identity draw) ->
-    ``frcnn_prep_image``; boxes, ``ignore`` and ``flipped`` of the local entry follow on the host."""
+    ``frcnn_prep_image``; boxes, ``ignore`` and ``flipped`` of the local entry follow on the host.  ``augment_en`` in test
+    mode (behind cfg.IMAGE.EN_TEST_SPATTER): file -> uint8 frame on the device -> ``frcnn_image_spatter`` ->
+    ``frcnn_prep_image``, the seed of the draws from the frame's file name and cfg.RNG_SEED (``draw_test_corruption``)."""
     from copy import deepcopy
     from ..utils.blob import im_list_to_blob, prep_im_for_blob
     _no_augmentation(augment_en, mode)
@@ -111,7 +117,10 @@ def _get_image_blob(roidb, im_scale, augment_en=False, mode='train', device='cud
     else:
         im, local_roidb = read_image_file(roidb[0]['filename']), deepcopy(roidb)
         local_roidb[0]['flipped'] = False
-    if augment_en:
+    if augment_en and mode == 'test':
+        from .image_augment import draw_test_corruption
+        im = ops.image_spatter(torch.from_numpy(im).to(device, non_blocking=True), draw_test_corruption(key=roidb[0]))
+    elif augment_en:
         from .image_augment import augment_image_gt_boxes, draw_image_augmentation
         height, width = int(im.shape[0]), int(im.shape[1])
         aug = draw_image_augmentation(width, height)

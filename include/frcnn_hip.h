@@ -500,6 +500,30 @@ int frcnn_image_augment(const uint8_t* img_hwc3, int h, int w, int flip, int num
                         const float* stage_params_host, uint32_t seed, const uint32_t* seed_dev, void* scratch,
                         size_t scratch_bytes, uint8_t* out, float* debug_pre, void* stream);
 
+/* Test-time Spatter corruption of a camera frame (lib/roi_data_layer/minibatch.py:648-664, iaa.imgcorruptlike.Spatter
+ * behind cfg.TEST.AUGMENT_EN), mud branch of the published ImageNet-C operator, in front of frcnn_prep_image: img / out are
+ * uint8 (h, w, 3) frames in cv2.imread order, one fused launch, no workspace.
+ *   params_host: FRCNN_SPATTER_NUM_PARAMS floats [loc, scale, sigma1, thr, sigma2] (the operator's constants of a severity).
+ *   taps1_host / taps2_host: the normalised Gaussian taps of sigma1 / sigma2, computed by the caller in double;
+ *     num_taps = 2 * int(4 sigma + 0.5) + 1 (skimage's radius rule; anything else is rejected), at most
+ *     FRCNN_SPATTER_MAX_TAPS1 / FRCNN_SPATTER_MAX_TAPS2, which is what the kernel's halo holds.
+ *   liquid = loc + scale * normal01(seed + *seed_dev, stream 44, y * w + x)  (csrc/rng.h; seed_dev device uint32 or NULL)
+ *   liquid = blur(liquid, taps1);  b = liquid > thr;  m = blur(b, taps2);  m = m < 0.8 ? 0 : m
+ *   out[c] = (uint8) (clip(img[c] / 255 * (1 - m) + mud[c] * m, 0, 1) * 255), truncated; mud = (63, 42, 20) / 255 on memory
+ *   channels 0, 1, 2 (the reference hands cv2's BGR frame to an RGB corruption: kept).  Blurs: separable, horizontal then
+ *   vertical, fp32, border replicate.  A pixel with m = 0 leaves unchanged.
+ * debug_liquid / debug_mask (device, h*w floats each, usually NULL): the field after the first blur, m before the 0.8 cut.
+ * FRCNN_ERR_ARG: a null img / out / params / taps pointer, h or w below 1, a tap count above what the kernel holds (or even,
+ * or off the radius rule), a non-finite number, out overlapping img.  No allocation, no host synchronisation; one kernel
+ * launch.  Restated from the published algorithm (imgaug / imagecorruptions / scikit-image absent: parity unpinned); the
+ * conventions are listed in csrc/image_spatter.hip. */
+#define FRCNN_SPATTER_NUM_PARAMS 5
+#define FRCNN_SPATTER_MAX_TAPS1 9
+#define FRCNN_SPATTER_MAX_TAPS2 13
+int frcnn_image_spatter(const uint8_t* img_hwc3, int h, int w, const float* params_host, const float* taps1_host, int num_taps1,
+                        const float* taps2_host, int num_taps2, uint32_t seed, const uint32_t* seed_dev, uint8_t* out,
+                        float* debug_liquid, float* debug_mask, void* stream);
+
 /* Scoring of one class's detections file: the overlap and matching loop the three evaluators share
  * (lib/datasets/waymo_eval.py:131-213, kitti_eval.py:116-215, cadc_eval.py:115-206, and the iou helper of the missing
  * lib/utils/eval_utils.py as restated in datasets/waymo_eval.py), one launch, one workgroup per frame.
