@@ -5,7 +5,7 @@ built by ``faster_rcnn_pytorch_multimodal_amd.build.build()`` (``__graft_entry__
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_size_t, c_uint32, c_void_p
 
 from .build import LIB_PATH
 
@@ -22,6 +22,7 @@ PROTOTYPES = {
     "frcnn_conv2d_fwd": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 11 + [_P, c_size_t, _P]),
     "frcnn_conv2d_fwd_pre": (c_int, [_P, _P, _P, _P, _P, _P, _P] + [c_int] * 11 + [_P, c_size_t, _P]),
     "frcnn_conv2d_winograd_filter_bytes": (c_size_t, [c_int, c_int]),
+    "frcnn_conv2d_winograd_rows": (c_long, [c_int, c_int, c_int, POINTER(c_long)]),
     "frcnn_conv2d_winograd_filter": (c_int, [_P, _P, c_int, c_int, _P]),
     "frcnn_conv2d_set_tile": (c_int, [c_int, c_int]),
     "frcnn_conv2d_set_staging": (c_int, [c_int]),

@@ -67,6 +67,10 @@ struct ConvParams {
   // grouped launch (blockIdx.y = group): element offsets of a group's activations / filter / output.  Used by the
   // Winograd path (16 independent GEMMs in one launch); 0 for an ordinary convolution (gridDim.y = 1).
   size_t gx, gw, gy;
+  // rows of a group's GEMM by the kind of its Winograd component (i, j) = (group >> 2, group & 3): [0] i != 3 and j != 3,
+  // [1] i == 3 only, [2] j == 3 only, [3] both (group_rows).  An ordinary convolution is group 0: [0] = M; a Winograd launch
+  // that trims the components of partial tiles (launch_winograd) has [1..3] <= [0] = M, an untrimmed one M four times
+  int grows[4];
   // optional activation-backward epilogue (data-gradient calls): y = mask[m][n] > 0 ? y * mscale[n] : 0 - the ReLU /
   // folded-BatchNorm backward of the layer BELOW, applied to this layer's input gradient before it is stored
   const float* mask;
@@ -109,7 +113,7 @@ __device__ __forceinline__ void tile_coords(int tile, int tiles_m, int tiles_n, 
 // batching keeps 4 loads in flight instead of a load->wait->store chain per element).
 template <int TM, int TN>
 __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)[TM][TN], int m0, int n0, int wr, int wc,
-                                              int lane, int gy = -1, int gz = -1) {
+                                              int lane, int mrows, int gy = -1, int gz = -1) {   // mrows: group_rows
   if (gy < 0) gy = blockIdx.y;                     // (the persistent kernel walks groups / splits itself)
   if (gz < 0) gz = blockIdx.z;
   const size_t goff = (size_t)gy * p.gy;   // grouped launches have neither a residual nor split-K slabs
@@ -119,7 +123,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int m = m0 + (wr * TM + i) * 32 + mlane;
-    if (m >= p.M) continue;
+    if (m >= mrows) continue;
     size_t orow = (size_t)m * p.K + goff;  // row of y / residual
     if (p.ys != 1) {
       const int img = m / (p.Ho * p.Wo);
@@ -192,7 +196,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
 // the wave is then 8 rows x 128 contiguous bytes.  Same per-element arithmetic -> bit-identical results.  K % 4 == 0 only.
 template <int TM, int TN>
 __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, f32x16 (&acc)[TM][TN], int m0, int n0, int wr, int wc,
-                                                  int lane, float* __restrict__ patch, int gy = -1, int gz = -1) {
+                                                  int lane, int mrows, float* __restrict__ patch, int gy = -1, int gz = -1) {
   if (gy < 0) gy = blockIdx.y;
   if (gz < 0) gz = blockIdx.z;
   const size_t goff = (size_t)gy * p.gy;
@@ -217,7 +221,7 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, f32x16 (&
         const int row = rrow + 8 * it;
         const int m = m0 + (wr * TM + i) * 32 + row;
         v[it] = *reinterpret_cast<const f32x4*>(patch + row * LDS_PITCH + rcol);
-        ok[it] = nok && m < p.M;
+        ok[it] = nok && m < mrows;
         size_t orow = (size_t)m * p.K + goff;
         if (p.ys != 1 && ok[it]) {
           const int img = m / (p.Ho * p.Wo);
@@ -280,6 +284,28 @@ __device__ __forceinline__ void tile_origin(const ConvParams& p, int block, int&
   n0 = tile_n * BN;
 }
 
+// Rows of group gy's GEMM (ConvParams::grows); the rows of a tile past them are neither loaded (zero page) nor stored.
+__device__ __forceinline__ int group_rows(const ConvParams& p, int gy) {
+  const bool i3 = (gy >> 2) == 3, j3 = (gy & 3) == 3;
+  return i3 ? (j3 ? p.grows[3] : p.grows[1]) : (j3 ? p.grows[2] : p.grows[0]);
+}
+
+// tile_origin for a group of `mrows` <= p.M rows: the group's OWN ceil(mrows / BM) x tiles_n tiles are laid over the first
+// workgroups of the grid (which is sized for p.M rows) and the rest return false - before their first barrier, the test is
+// uniform.  Remapping p.tiles_m x tiles_n and dropping the tiles past mrows instead would leave the XCDs that own the last
+// m-tiles (xcd_remap hands each XCD a contiguous range) without work in the trimmed groups while the first XCD still walks
+// all of its tiles: the launch would take as long as the untrimmed one.  mrows == p.M: exactly tile_origin.
+template <int BM, int BN>
+__device__ __forceinline__ bool group_tile_origin(const ConvParams& p, int block, int mrows, int& m0, int& n0) {
+  const int tiles_m = (mrows + BM - 1) / BM, ntiles = tiles_m * p.tiles_n;
+  if (block >= ntiles) return false;
+  int tile_m, tile_n;
+  tile_coords(xcd_remap(block, ntiles), tiles_m, p.tiles_n, tile_m, tile_n);
+  m0 = tile_m * BM;
+  n0 = tile_n * BN;
+  return true;
+}
+
 // K-split z reduces the K-steps [begin, begin + returned count); the count is <= 0 for a split past the end
 __device__ __forceinline__ int split_range(const ConvParams& p, int z, int& begin) {
   begin = z * p.steps_per_split;
@@ -318,7 +344,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_f32(const ConvPara
   const float* const pw = p.w + (size_t)blockIdx.y * p.gw;
 
   int m0, n0;
-  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+  const int mrows = group_rows(p, blockIdx.y);
+  if (!group_tile_origin<BM, BN>(p, blockIdx.x, mrows, m0, n0)) return;
 
   const int step_begin = blockIdx.z * p.steps_per_split;   // (split_range written out: nsteps is formed below, where it is used)
   const int step_end = min(step_begin + p.steps_per_split, p.ksteps);
@@ -356,7 +383,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_f32(const ConvPara
 #pragma unroll
   for (int i = 0; i < PA; ++i) {
     const int m = m0 + i * RPP + row0;
-    if (!WINO && m < p.M) {
+    if (!WINO && m < mrows) {
       const int img = m / (p.Ho * p.Wo);
       const int rem = m - img * p.Ho * p.Wo;
       const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
@@ -512,9 +539,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_f32(const ConvPara
   }
 
   if (p.epi_lds && (p.K & 3) == 0)   // (uniform branch; every wave is past the K loop's last barrier and reads no LDS any more)
-    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, smem + wave * 32 * LDS_PITCH);
+    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows, smem + wave * 32 * LDS_PITCH);
   else
-    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane);
+    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -541,7 +568,8 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
   const float* const px = p.x + (size_t)blockIdx.y * p.gx;
   const float* const pw = p.w + (size_t)blockIdx.y * p.gw;
   int m0, n0, step_begin;
-  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+  const int mrows = group_rows(p, blockIdx.y);
+  if (!group_tile_origin<BM, BN>(p, blockIdx.x, mrows, m0, n0)) return;
   const int nsteps = split_range(p, blockIdx.z, step_begin);
 
   // ---- per-lane sources: lane i of instruction q feeds row 8q + (i >> 3), physical chunk i & 7 -------------
@@ -552,7 +580,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
     const int row = (wave * PA + j) * 8 + lrow;
     const int m = m0 + row;
     a_swz[j] = swizzled_chunk(row, lchunk) * 4;
-    if (m < p.M) {
+    if (m < mrows) {
       const int img = m / (p.Ho * p.Wo);
       const int rem = m - img * p.Ho * p.Wo;
       const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
@@ -683,9 +711,9 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_f32(const ConvParams p)
   }
   if (p.epi_lds && (p.K & 3) == 0) {
     __syncthreads();   // the last step has no barrier behind its fragment reads: every wave must be done with the stages
-    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, smem + wave * 32 * LDS_PITCH);
+    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows, smem + wave * 32 * LDS_PITCH);
   } else {
-    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane);
+    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows);
   }
 }
 
@@ -711,7 +739,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
   const float* const px = p.x + (size_t)blockIdx.y * p.gx;
   const float* const pw = p.w + (size_t)blockIdx.y * p.gw;
   int m0, n0, step_begin;
-  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+  const int mrows = group_rows(p, blockIdx.y);
+  if (!group_tile_origin<BM, BN>(p, blockIdx.x, mrows, m0, n0)) return;
   const int nsteps = split_range(p, blockIdx.z, step_begin);
 
   // ---- per-lane sources: lane i of instruction q feeds row 8q + (i >> 3), physical chunk i & 7 -------------
@@ -722,7 +751,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
     const int row = (wave * PA + j) * 8 + lrow;
     const int m = m0 + row;
     a_swz[j] = swizzled_chunk(row, lchunk) * 4;
-    if (m < p.M) {
+    if (m < mrows) {
       const int img = m / (p.Ho * p.Wo);
       const int rem = m - img * p.Ho * p.Wo;
       const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
@@ -849,9 +878,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma2_f32(const ConvParams p
   }
   if (p.epi_lds && (p.K & 3) == 0) {
     __syncthreads();
-    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, smem + wave * 32 * LDS_PITCH);
+    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows, smem + wave * 32 * LDS_PITCH);
   } else {
-    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane);
+    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows);
   }
 }
 
@@ -889,7 +918,8 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
   const int lane = t & 63, wave = t >> 6;
   const int wr = wave / WN, wc = wave % WN;
   int m0, n0, step_begin;
-  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+  const int mrows = group_rows(p, blockIdx.y);
+  if (!group_tile_origin<BM, BN>(p, blockIdx.x, mrows, m0, n0)) return;
   const int nsteps = split_range(p, blockIdx.z, step_begin);
 
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
@@ -906,7 +936,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
     const int row = (wave * PA + j) * 8 + lrow;
     const int m = m0 + row;
     a_swz[j] = (unsigned)(swizzled_chunk(row, lchunk) * 16);
-    if (m < p.M) {
+    if (m < mrows) {
       const int img = m / (p.Ho * p.Wo);
       const int rem = m - img * p.Ho * p.Wo;
       const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
@@ -1028,9 +1058,9 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN == 1) ? 3 : 2) void conv_ige
   }
   if (p.epi_lds && (p.K & 3) == 0) {
     __syncthreads();   // the last step has no barrier behind its fragment reads: every wave must be done with the stages
-    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, smem + wave * 32 * LDS_PITCH);
+    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows, smem + wave * 32 * LDS_PITCH);
   } else {
-    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane);
+    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane, mrows);
   }
 }
 
@@ -1211,8 +1241,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_pbuf_f32(const ConvParams p
       stage = next;
       --ahead;
     }
-    if (p.epi_lds && (p.K & 3) == 0) conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, patch, g, z);
-    else conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane, g, z);
+    if (p.epi_lds && (p.K & 3) == 0) conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, p.M, patch, g, z);
+    else conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane, p.M, g, z);
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
   }
@@ -1354,6 +1384,7 @@ constexpr int kNumShapes = 6;   // rows 0 .. kNumShapes - 1 hold every tile shap
 // the rows the code names: the mid-size tile (choose_plan's start, forced Winograd) and the small one (the fall-back of a
 // forced split, the small forced-Winograd GEMM, the ONLY tile of the fused Winograd input transform)
 constexpr int kTile128x128 = 2, kTile64x64 = 5;
+constexpr int kTilePersistent = 13;   // (launch_winograd: this row's kernel takes every group's row count from p.M)
 static_assert(kTiles[kTile128x128].tm == 2 && kTiles[kTile128x128].tn == 2 && kTiles[kTile64x64].tm == 1 && kTiles[kTile64x64].tn == 1 &&
               kTile128x128 < kNumShapes && kTile64x64 < kNumShapes, "the named rows are the register-staged 128x128 and 64x64 tiles");
 
@@ -1406,6 +1437,9 @@ std::atomic<int> g_algo_mode{0};   // atomic: set from one thread while another 
 std::atomic<int> g_wino_fuse{1};
 // test / tuning hook (frcnn_conv2d_set_algo bit 6): 1 = the convolution kernels store through the LDS transpose
 std::atomic<int> g_epi_lds{1};
+// test / tuning hook (frcnn_conv2d_set_algo bit 7): 1 = Winograd leaves out the components of partial tiles that feed only
+// dropped outputs (wino_geom), 0 = every tile carries all 16 components
+std::atomic<int> g_wino_trim{1};
 
 // device address of g_zero_page, resolved once (hipGetSymbolAddress is a host-side lookup: legal during stream capture)
 const float* zero_page_address() {
@@ -1547,13 +1581,15 @@ extern "C" int frcnn_conv2d_set_tile(int tm, int tn) {
 }
 
 extern "C" int frcnn_conv2d_set_algo(int mode) {
-  FRCNN_REQUIRE(mode >= 0 && (mode & 3) <= 2 && (mode & ~(3 | 16 | 32 | 64)) == 0,
+  FRCNN_REQUIRE(mode >= 0 && (mode & 3) <= 2 && (mode & ~(3 | 16 | 32 | 64 | 128)) == 0,
                 "conv2d_set_algo: mode %d (0 auto, 1 implicit GEMM only, 2 Winograd where it applies; +16: never fuse the "
                 "Winograd input transform into the GEMM, +32: forced Winograd uses the 64x64 GEMM with the fused transform, +64: the "
-                "register-staged kernels store straight from the MFMA layout instead of through the LDS transpose)", mode);
+                "register-staged kernels store straight from the MFMA layout instead of through the LDS transpose, +128: Winograd "
+                "never trims the components of partial tiles)", mode);
   g_algo_mode = mode & 3;
   g_wino_fuse = (mode & 16) ? 0 : ((mode & 32) ? 2 : 1);
   g_epi_lds = (mode & 64) ? 0 : 1;
+  g_wino_trim = (mode & 128) ? 0 : 1;
   return FRCNN_OK;
 }
 
@@ -1612,6 +1648,7 @@ bool frcnn::autotune_enabled() { return g_autotune != 0; }
 
 unsigned long long frcnn::conv_settings_word() {
   return (unsigned long long)g_algo_mode.load() | ((unsigned long long)g_wino_fuse.load() << 4) |
+         ((unsigned long long)(g_wino_trim.load() ? 0 : 1) << 6) |
          ((unsigned long long)g_epi_lds.load() << 8) | ((unsigned long long)g_use_dma.load() << 12) |
          ((unsigned long long)g_force_tm.load() << 16) | ((unsigned long long)g_force_tn.load() << 24);
 }
@@ -1689,21 +1726,55 @@ namespace {
 // Four launches: filter transform (stateless ABI: recomputed per call, 16 KC floats), input transform, ONE grouped
 // launch of the implicit-GEMM kernels as a 1x1 convolution (blockIdx.y = transform component), output transform with
 // the BatchNorm scale / shift and ReLU.  Only the autotuner selects it (choose_plan never does).
+//
+// Trimmed components.  A map with odd H has a last tile row whose second output row falls off the map; in Y = A^T M A,
+// A^T = [[1,1,1,0],[0,1,-1,-1]], component row i = 3 feeds nothing but that output row, so the four components (3, j) of
+// such a tile are never used - likewise (i, 3) in the last tile column of a map with odd W.  They are not computed: with
+// eh = H & 1, ew = W & 1, fh = th - eh, fw = tw - ew the tiles fall into four classes, interior (n fh fw tiles), right edge
+// (n fh ew), bottom edge (n eh fw) and corner (n eh ew), and the rows of a component's plane are class-major
+// [interior | right | bottom | corner] with the classes that lack the component left out:
+//   i != 3, j != 3 (9 components): T rows          i == 3, j != 3 (3): nI + nR rows
+//   i != 3, j == 3 (3): nI + nB rows               i == 3, j == 3 (1): nI rows
+// so the grouped GEMM runs 9 T + 3 (nI + nR) + 3 (nI + nB) + nI rows instead of 16 T (67 500 instead of 76 800 on the
+// 300 RoIs x 7 x 7 of layer4: -12.1 %; nothing changes on an even x even map, where nI = T and this IS the plain tile order),
+// and V and M shrink alike.  Planes keep their stride T C / T K (the trimmed ones are sparse at their tail; the workspace
+// layout does not change), U stays (16, K, C).  Every surviving M[comp][tile][k] is the same k-ordered fma chain and every
+// output the same sum of the same components: no output bit changes.  frcnn_conv2d_set_algo flag 128 turns it off (A/B).
 // ------------------------------------------------------------------------------------------------
 bool winograd_ok(int r, int s, int stride, int pad, int c, int k, int out_stride) {
   return r == 3 && s == 3 && stride == 1 && pad == 1 && (c % 4) == 0 && (k % 4) == 0 && out_stride == 1;
 }
 
+// tile classes of the trimmed layout, as the transform kernels need them (kernel argument)
+struct WinoClasses {
+  int fh, fw;        // tile rows / columns whose 2x2 outputs are all inside the map
+  int eh, ew;        // 1: a partial last tile row / column exists and its unused components are left out
+  long nI, nR, nB;   // interior, right-edge and bottom-edge tiles in the batch (the corner tiles follow them)
+};
 struct WinoGeom {
   int th, tw;        // 2x2 output tiles per image
   long T;            // tiles in the batch
   size_t u_off, v_off, m_off, bytes;   // workspace layout (bytes)
+  WinoClasses cl;
+  long rows[4];      // GEMM rows by component kind, the order of ConvParams::grows
 };
-WinoGeom wino_geom(int n, int h, int w, int c, int k) {
+// trim = false: every tile is an interior tile of the plain (n, ty, tx) order and every component has T rows
+WinoGeom wino_geom(int n, int h, int w, int c, int k, bool trim = false) {
   WinoGeom g;
   g.th = (h + 1) / 2;
   g.tw = (w + 1) / 2;
   g.T = (long)n * g.th * g.tw;
+  g.cl.eh = trim ? (h & 1) : 0;
+  g.cl.ew = trim ? (w & 1) : 0;
+  g.cl.fh = g.th - g.cl.eh;
+  g.cl.fw = g.tw - g.cl.ew;
+  g.cl.nI = (long)n * g.cl.fh * g.cl.fw;
+  g.cl.nR = (long)n * g.cl.fh * g.cl.ew;
+  g.cl.nB = (long)n * g.cl.eh * g.cl.fw;
+  g.rows[0] = g.T;
+  g.rows[1] = g.cl.nI + g.cl.nR;
+  g.rows[2] = g.cl.nI + g.cl.nB;
+  g.rows[3] = g.cl.nI;
   g.u_off = 0;
   g.v_off = frcnn::align_up((size_t)16 * k * c * sizeof(float), 256);
   g.m_off = g.v_off + frcnn::align_up((size_t)16 * g.T * c * sizeof(float), 256);
@@ -1745,10 +1816,30 @@ __global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restric
   }
 }
 
-// V[i*4+j][t][c] = (B^T d B)[i][j] of the 4x4 input patch of tile t (rows 2ty-1.., cols 2tx-1.., zero outside the map);
+// Row of tile (n, ty, tx) in the planes of the four component kinds (the order of ConvParams::grows), -1 where the tile's
+// class lacks the component.  Untrimmed (eh = ew = 0) every tile is interior and all four are the plain tile index.
+__device__ __forceinline__ void wino_tile_rows(const WinoClasses& cl, int n, int ty, int tx, long (&row)[4]) {
+  const bool be = cl.eh && ty == cl.fh, re = cl.ew && tx == cl.fw;
+  if (!be && !re) {
+    row[0] = row[1] = row[2] = row[3] = ((long)n * cl.fh + ty) * cl.fw + tx;
+  } else if (!be) {                        // right edge: no component (i, 3)
+    row[0] = row[1] = cl.nI + (long)n * cl.fh + ty;
+    row[2] = row[3] = -1;
+  } else if (!re) {                        // bottom edge: no component (3, j)
+    row[0] = cl.nI + cl.nR + (long)n * cl.fw + tx;
+    row[2] = cl.nI + (long)n * cl.fw + tx;
+    row[1] = row[3] = -1;
+  } else {                                 // corner: neither
+    row[0] = cl.nI + cl.nR + cl.nB + n;
+    row[1] = row[2] = row[3] = -1;
+  }
+}
+
+// V[i*4+j][row][c] = (B^T d B)[i][j] of the 4x4 input patch of tile t (rows 2ty-1.., cols 2tx-1.., zero outside the map);
 // B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]].  One thread per (tile, 4 channels): lanes run along the channels.
+// Only the components the tile's class has are written, at the tile's row in that component's plane (wino_tile_rows).
 __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, float* __restrict__ V, int H, int W,
-                                                        int C4, int th, int tw, long T) {
+                                                        int C4, int th, int tw, long T, const WinoClasses cl) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)T * C4) return;
   const int c4 = (int)(idx % C4);
@@ -1777,23 +1868,30 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
     r[2][j] = d[2][j] - d[1][j];
     r[3][j] = d[1][j] - d[3][j];
   }
-  f32x4* dst = reinterpret_cast<f32x4*>(V) + (size_t)t * C4 + c4;
+  long row[4];
+  wino_tile_rows(cl, n, ty, tx, row);
+  f32x4* dst = reinterpret_cast<f32x4*>(V) + c4;
   const size_t plane = (size_t)T * C4;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    dst[(size_t)(i * 4 + 0) * plane] = r[i][0] - r[i][2];
-    dst[(size_t)(i * 4 + 1) * plane] = r[i][1] + r[i][2];
-    dst[(size_t)(i * 4 + 2) * plane] = r[i][2] - r[i][1];
-    dst[(size_t)(i * 4 + 3) * plane] = r[i][1] - r[i][3];
+    const long ra = row[i == 3 ? 1 : 0], rb = row[i == 3 ? 3 : 2];     // components (i, 0..2) and (i, 3)
+    if (ra >= 0) {
+      dst[(size_t)(i * 4 + 0) * plane + (size_t)ra * C4] = r[i][0] - r[i][2];
+      dst[(size_t)(i * 4 + 1) * plane + (size_t)ra * C4] = r[i][1] + r[i][2];
+      dst[(size_t)(i * 4 + 2) * plane + (size_t)ra * C4] = r[i][2] - r[i][1];
+    }
+    if (rb >= 0) dst[(size_t)(i * 4 + 3) * plane + (size_t)rb * C4] = r[i][1] - r[i][3];
   }
 }
 
-// y[2ty+a][2tx+b] = act((A^T m A)[a][b] * scale + shift),  A^T = [[1,1,1,0],[0,1,-1,-1]];  one thread per (tile, 4 channels)
+// y[2ty+a][2tx+b] = act((A^T m A)[a][b] * scale + shift),  A^T = [[1,1,1,0],[0,1,-1,-1]];  one thread per (tile, 4 channels).
+// A component the tile's class lacks is NOT loaded (its rows were never written; the workspace may hold anything): the sums
+// it would enter (s1 of a bottom tile, column 3 of a right one) feed only the outputs dropped below and are left at zero.
 __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ Mo, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, float* __restrict__ y, int H,
                                                          int W, int K4, int th, int tw, long T, int relu,
                                                          const float* __restrict__ mask,
-                                                         const float* __restrict__ mscale) {
+                                                         const float* __restrict__ mscale, const WinoClasses cl) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)T * K4) return;
   const int k4 = (int)(idx % K4);
@@ -1802,14 +1900,22 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
   const long t2 = t / tw;
   const int ty = (int)(t2 % th);
   const int n = (int)(t2 / th);
-  const f32x4* src = reinterpret_cast<const f32x4*>(Mo) + (size_t)t * K4 + k4;
+  long row[4];
+  wino_tile_rows(cl, n, ty, tx, row);
+  const f32x4* src = reinterpret_cast<const f32x4*>(Mo) + k4;
   const size_t plane = (size_t)T * K4;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   f32x4 s0[4], s1[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const f32x4 m0 = src[(size_t)(0 * 4 + j) * plane], m1 = src[(size_t)(1 * 4 + j) * plane];
-    const f32x4 m2 = src[(size_t)(2 * 4 + j) * plane], m3 = src[(size_t)(3 * 4 + j) * plane];
+    const long ra = row[j == 3 ? 2 : 0], rb = row[j == 3 ? 3 : 1];     // components (0..2, j) and (3, j)
+    s0[j] = s1[j] = zero;
+    if (ra < 0) continue;
+    const f32x4 m0 = src[(size_t)(0 * 4 + j) * plane + (size_t)ra * K4], m1 = src[(size_t)(1 * 4 + j) * plane + (size_t)ra * K4];
+    const f32x4 m2 = src[(size_t)(2 * 4 + j) * plane + (size_t)ra * K4];
     s0[j] = m0 + m1 + m2;
+    if (rb < 0) continue;
+    const f32x4 m3 = src[(size_t)(3 * 4 + j) * plane + (size_t)rb * K4];
     s1[j] = m1 - m2 - m3;
   }
   f32x4 o[2][2];
@@ -1868,7 +1974,10 @@ int launch_1d(const char* what, size_t threads, hipStream_t stream, Args... args
 int launch_winograd(const ConvParams& p, const Plan& pl, const float* scale, const float* shift, float* y, int relu,
                     void* ws, hipStream_t stream) {
   const int n = p.M / (p.Ho * p.Wo);
-  const WinoGeom g = wino_geom(n, p.H, p.W, p.C, p.K);
+  // The fused input transform (conv_igemm_f32<.., WINO>) reads the map in plain tile order and the persistent kernel (tile
+  // kTilePersistent) walks p.M rows of every group: plans with either run the untrimmed form, which is bit-identical anyway.
+  const bool trim = g_wino_trim && !pl.fuse_in && pl.cfg != kTilePersistent;
+  const WinoGeom g = wino_geom(n, p.H, p.W, p.C, p.K, trim);
   char* base = static_cast<char*>(ws);
   float* U = reinterpret_cast<float*>(base + g.u_off);
   float* V = reinterpret_cast<float*>(base + g.v_off);
@@ -1879,13 +1988,14 @@ int launch_winograd(const ConvParams& p, const Plan& pl, const float* scale, con
   if (rc != FRCNN_OK) return rc;
   if (!pl.fuse_in)
     rc = launch_1d<wino_input_kernel>("wino_input_kernel", (size_t)g.T * (p.C / 4), stream, p.x, V, p.H, p.W, p.C / 4, g.th,
-                   g.tw, g.T);
+                   g.tw, g.T, g.cl);
   if (rc != FRCNN_OK) return rc;
   // 16 GEMMs  Mo[xi] (T x K) = V[xi] (T x C) . U[xi]^T (K x C)  as ONE grouped 1x1 convolution over a 1 x T "image"
   ConvParams q;
   q.x = V; q.w = U; q.scale = nullptr; q.shift = nullptr; q.res = nullptr; q.y = Mo; q.partial = nullptr;
   q.H = 1; q.W = (int)g.T; q.C = p.C; q.K = p.K; q.R = 1; q.S = 1; q.stride = 1; q.pad = 0; q.Ho = 1; q.Wo = (int)g.T;
   q.M = (int)g.T;
+  for (int i = 0; i < 4; ++i) q.grows[i] = (int)g.rows[i];
   q.Ktot = p.C;
   q.ksteps = (p.C + BK - 1) / BK;
   q.relu = 0;
@@ -1911,7 +2021,7 @@ int launch_winograd(const ConvParams& p, const Plan& pl, const float* scale, con
   rc = launch_gemm(q, gp, g.T, p.K, 16, stream);
   if (rc != FRCNN_OK) return rc;
   return launch_1d<wino_output_kernel>("wino_output_kernel", (size_t)g.T * (p.K / 4), stream, (const float*)Mo, scale, shift, y,
-                   p.Ho, p.Wo, p.K / 4, g.th, g.tw, g.T, relu, p.mask, p.mscale);
+                   p.Ho, p.Wo, p.K / 4, g.th, g.tw, g.T, relu, p.mask, p.mscale, g.cl);
 }
 
 int launch_plan(ConvParams p, const Plan& pl, long M, int k, const float* scale, const float* shift,
@@ -2072,6 +2182,7 @@ int run_conv(const float* x, const float* wgt, const float* scale, const float* 
   p.ys = out_stride; p.Hy = hy; p.Wy = wy;
   p.steps_per_split = p.ksteps; p.tiles_m = p.tiles_n = 0;
   p.gx = p.gw = p.gy = 0;
+  p.grows[0] = p.grows[1] = p.grows[2] = p.grows[3] = p.M;
   p.wiH = p.wiW = p.wth = p.wtw = 0;
   p.epi_lds = g_epi_lds;
   {
@@ -2141,6 +2252,15 @@ extern "C" int frcnn_conv2d_fwd(const float* x, const float* wgt, const float* s
 extern "C" size_t frcnn_conv2d_winograd_filter_bytes(int k, int c) {
   if (k <= 0 || c <= 0 || (k % 4) || (c % 4)) return 0;
   return (size_t)16 * k * c * sizeof(float);
+}
+
+extern "C" long frcnn_conv2d_winograd_rows(int n, int h, int w, long out[4]) {
+  if (out) out[0] = out[1] = out[2] = out[3] = 0;
+  if (n <= 0 || h <= 0 || w <= 0 || (long)n * ((h + 1) / 2) * ((w + 1) / 2) > INT32_MAX) return 0;
+  const WinoGeom g = wino_geom(n, h, w, 4, 4, g_wino_trim != 0);
+  if (out)
+    for (int i = 0; i < 4; ++i) out[i] = g.rows[i];
+  return 9 * g.rows[0] + 3 * g.rows[1] + 3 * g.rows[2] + g.rows[3];
 }
 
 extern "C" int frcnn_conv2d_winograd_filter(const float* w_krsc, float* u, int k, int c, void* stream_) {

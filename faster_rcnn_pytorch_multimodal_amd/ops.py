@@ -80,7 +80,9 @@ def set_conv_autotune(enable):
 def set_conv_algo(mode):
     """0 = the autotuner may choose Winograd F(2x2, 3x3) for the eligible 3x3 layers, 1 = implicit GEMM only,
     2 = Winograd wherever it applies (frcnn_conv2d_set_algo).  Flags: +16 never fuse the Winograd input transform into the
-    64x64 GEMM's tile load, +32 forced Winograd (2) uses that fused form wherever C % 32 == 0 (tests)."""
+    64x64 GEMM's tile load, +32 forced Winograd (2) uses that fused form wherever C % 32 == 0 (tests), +128 Winograd never
+    trims the transform components of partial tiles (odd map height / width) that feed only outputs outside the map - the
+    default leaves them out in every mode, bit for bit the same result (A/B timing and tests; see ``winograd_rows``)."""
     global _CONV_ALGO_MODE, _CONV_ALGO_FLAGS
     _hip.check(_hip.load().frcnn_conv2d_set_algo(int(mode)), "frcnn_conv2d_set_algo")
     _CONV_ALGO_MODE = int(mode) & 3
@@ -107,6 +109,14 @@ def winograd_filter_wanted(n, h, w, c, k, r, s, stride, pad):
         return True
     algo = conv_plan_algo(n, h, w, c, k, r, s, stride, pad, False)
     return algo == 1 or (algo < 0 and _CONV_AUTOTUNE)
+
+
+def winograd_rows(n, h, w):
+    """(rows of the four component kinds, rows summed over the 16 components) that the grouped Winograd GEMM of an
+    n x h x w map executes under the current ``set_conv_algo`` flags (frcnn_conv2d_winograd_rows; host only)."""
+    out = (ctypes.c_long * 4)()
+    total = _hip.load().frcnn_conv2d_winograd_rows(int(n), int(h), int(w), out)
+    return [int(v) for v in out], int(total)
 
 
 def conv_profile_begin():

@@ -186,8 +186,19 @@ int frcnn_conv2d_set_staging(int use_lds_dma);
  * Bottleneck, the RPN 3x3 of the Network):  0 (default) = the autotuner times the implicit GEMM and Winograd F(2x2, 3x3)
  * (same fp32 arithmetic, 2.25x fewer multiplications, four launches) and keeps the faster; without autotuning the
  * implicit GEMM runs;  1 = implicit GEMM only;  2 = Winograd wherever it applies (tests).  A Winograd plan is exported
- * with 16 added to its tile index. */
+ * with 16 added to its tile index.
+ * Flags (tests, A/B timing): +16 never fuse the Winograd input transform into the GEMM, +32 forced Winograd uses the 64x64
+ * GEMM with the fused transform, +64 the register-staged kernels store straight from the MFMA layout, +128 Winograd never
+ * trims: by default the transform components of a partial 2x2 tile (last tile row of a map with odd h, last tile column
+ * with odd w) that feed only outputs outside the map are neither transformed nor multiplied, which changes no output bit. */
 int frcnn_conv2d_set_algo(int mode);
+/* Host only: the rows the grouped Winograd GEMM of an n x h x w map executes under the current setting.  With
+ * th = (h+1)/2, tw = (w+1)/2, T = n th tw tiles, eh = h & 1, ew = w & 1 and nI = n (th-eh)(tw-ew), nR = n (th-eh) ew,
+ * nB = n eh (tw-ew): out[0] = T (each of the 9 components i != 3, j != 3), out[1] = nI + nR (3 components i == 3),
+ * out[2] = nI + nB (3 components j == 3), out[3] = nI (component (3,3)); all T with flag 128 set.  Returns the sum over
+ * the 16 components, 9 out[0] + 3 out[1] + 3 out[2] + out[3] (0 for a bad shape).  Plans with the fused input transform or the
+ * persistent tile (index 13) always run 16 T rows.  out may be NULL. */
+long frcnn_conv2d_winograd_rows(int n, int h, int w, long out[4]);
 
 /* The filter side of a Winograd plan is constant while the weights are: U[16][k][c] = G g G^T of a (k,3,3,c) filter,
  * computed once per parameter version by the caller and handed to frcnn_conv2d_fwd_pre, which is frcnn_conv2d_fwd
