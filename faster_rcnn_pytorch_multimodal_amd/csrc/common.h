@@ -29,7 +29,7 @@ hipError_t fill_bytes(void* dst, int value, size_t bytes, hipStream_t stream);
 hipError_t copy_bytes(void* dst, const void* src, size_t bytes, hipStream_t stream);
 
 // frcnn_settings_signature(): a hash of the CURRENT VALUES of every process-wide switch that changes which kernels an entry
-// point launches (frcnn_set_memops_mode, frcnn_conv2d_set_tile / _set_algo / _set_staging, frcnn_roi_align_set_variant,
+// point launches (frcnn_set_memops_mode, frcnn_conv2d_set_tile / _set_algo / _set_staging / frcnn_conv2d_bf16_set_tile, frcnn_roi_align_set_variant,
 // frcnn_filter_set_variant, frcnn_nms_set_suppress_at_equal, frcnn_conv2d_wgrad_set_variant).  A holder of captured graphs keys its captures by it: switching a
 // setting away and back finds the old captures again.  Each translation unit reports its own switches.
 unsigned long long conv_settings_word();

@@ -1559,6 +1559,8 @@ bool lookup_plan(const ShapeKey& key, Plan* pl) {
 
 // tuning hook: 0 = register-staged kernels only, 1 = LDS-DMA kernel for the 8-wave tiles when C % 32 == 0
 std::atomic<int> g_use_dma{1};
+// test / timing hook (frcnn_conv2d_bf16_set_tile): 0 = bf16_small_tile's rule, 1 = 64x64, 2 = 128x128
+std::atomic<int> g_bf16_tile{0};
 
 bool conv_args_ok(int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
   return n > 0 && h > 0 && w > 0 && c > 0 && (c % 4) == 0 && k > 0 && r > 0 && s > 0 && stride > 0 && pad >= 0 &&
@@ -1650,7 +1652,8 @@ unsigned long long frcnn::conv_settings_word() {
   return (unsigned long long)g_algo_mode.load() | ((unsigned long long)g_wino_fuse.load() << 4) |
          ((unsigned long long)(g_wino_trim.load() ? 0 : 1) << 6) |
          ((unsigned long long)g_epi_lds.load() << 8) | ((unsigned long long)g_use_dma.load() << 12) |
-         ((unsigned long long)g_force_tm.load() << 16) | ((unsigned long long)g_force_tn.load() << 24);
+         ((unsigned long long)g_force_tm.load() << 16) | ((unsigned long long)g_force_tn.load() << 24) |
+         ((unsigned long long)g_bf16_tile.load() << 32);
 }
 
 extern "C" int frcnn_conv2d_clear_plans(void) {
@@ -2234,7 +2237,256 @@ int run_conv(const float* x, const float* wgt, const float* scale, const float* 
   }
   return launch_plan(p, pl, M, k, scale, shift, residual, y, relu, ws, stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// bf16-operand forward convolution (frcnn_conv2d_fwd_bf16): the GEMM of conv_igemm_f32<..., ALIGNED = true> on
+// v_mfma_f32_32x32x16_bf16 - sixteen k per instruction, fp32 accumulation.  Activations and outputs stay fp32 NHWC in
+// HBM: an activation chunk is rounded to bf16 (nearest even, v_cvt_pk_bf16_f32) between its global load and its LDS
+// store; the filter arrives packed (frcnn_conv2d_pack_bf16, KRSC 16-bit words).  A K-step is 32 channels of one tap
+// (C % 32 == 0) = two MFMA groups of k = 16.
+//   LDS: rows of 32 bf16 at an 80-byte pitch, two stages.  A fragment is one ds_read_b128: lane l holds row l & 31,
+//   k = 8 (l >> 5) + j; the sixteen lanes of a read group hit sixteen distinct 16-byte slots (5 m mod 16 is a bijection).
+//   The C/D lane map is the fp32 instruction's, so tile_origin, the zero page and both epilogues are shared as they are.
+// 4 waves on a 128x128 (TM = TN = 2) or 64x64 (TM = TN = 1) tile; both walk K in the same order with the same
+// instruction, so their results are bit-identical.
+// ------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // eight packed bf16 in flight between the global load and the LDS store
+constexpr int BF16_PITCH = 80;   // bytes per LDS row (32 bf16 + 16 B pad)
+
+template <int TM, int TN, int DEPTH>
+__global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const ConvParams p, const unsigned short* __restrict__ wq) {
+  static_assert(DEPTH >= 1 && DEPTH <= 4, "register sets of the staging ring");
+  constexpr int WN = 2;
+  constexpr int BM = 64 * TM, BN = 64 * TN;
+  constexpr int PA = BM / 32;   // A: 8 threads x 4 floats cover a row's K-step, 32 rows per pass
+  constexpr int PB = BN / 64;   // B: 4 threads x 8 bf16 cover a row's K-step, 64 rows per pass
+  static_assert(2 * (BM + BN) * BF16_PITCH >= 4 * 32 * LDS_PITCH * (int)sizeof(float), "the epilogue's patches fit the stages");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* const As = reinterpret_cast<char*>(smem);   // [2][BM][80 B]
+  char* const Bs = As + 2 * BM * BF16_PITCH;        // [2][BN][80 B]
+
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int wr = wave / WN, wc = wave % WN;
+  int m0, n0;
+  tile_origin<BM, BN>(p, blockIdx.x, m0, n0);
+
+  const int kc = t & 7, row0 = t >> 3;
+  int a_base[PA], a_hi0[PA], a_wi0[PA];
+#pragma unroll
+  for (int i = 0; i < PA; ++i) {
+    const int m = m0 + i * 32 + row0;
+    if (m < p.M) {
+      const int img = m / (p.Ho * p.Wo);
+      const int rem = m - img * p.Ho * p.Wo;
+      const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
+      a_hi0[i] = ho * p.stride - p.pad;
+      a_wi0[i] = wo * p.stride - p.pad;
+      a_base[i] = ((img * p.H + a_hi0[i]) * p.W + a_wi0[i]) * p.C;
+    } else {
+      a_hi0[i] = -(1 << 20);  // never in range
+      a_wi0[i] = 0;
+      a_base[i] = 0;
+    }
+  }
+  const int kb = t & 3, rowb = t >> 2;
+  const unsigned short* b_src[PB];
+#pragma unroll
+  for (int j = 0; j < PB; ++j) {
+    const int n = n0 + j * 64 + rowb;
+    b_src[j] = n < p.K ? wq + (size_t)n * p.Ktot + kb * 8 : nullptr;
+  }
+
+  // DEPTH register sets: tile t waits in set t % DEPTH from its global load until step t - 1 stores it to LDS, so the tiles
+  // of steps s+1 .. s+DEPTH are in flight while step s computes.  A step's MFMAs are an eighth of the fp32 kernel's for the
+  // same tile: with one tile ahead a lone 64x64 workgroup pays the HBM / L2 latency once per K-step (DEPTH = 4 there); the
+  // 128x128 tile keeps one set - 154 VGPRs, three workgroups per CU - because a deeper ring costs it the third workgroup.
+  f32x4 ra[DEPTH][PA];
+  u32x4 rb[DEPTH][PB];
+  typedef std::integral_constant<int, 0> Set0;
+  typedef std::integral_constant<int, 1 % DEPTH> Set1;   // SetN: the set of tile N
+  typedef std::integral_constant<int, 2 % DEPTH> Set2;
+  typedef std::integral_constant<int, 3 % DEPTH> Set3;
+  int tr = 0, ts = 0, tc = 0;   // tap state: a K-step never straddles a tap
+  // load_tiles is called for consecutive steps (the tap state advances by one step per call)
+  auto load_tiles = [&](int step, auto set) {
+    constexpr int SL = decltype(set)::value;
+    const int koff = (tr * p.W + ts) * p.C + tc + kc * 4;
+#pragma unroll
+    for (int i = 0; i < PA; ++i) {
+      const int hi = a_hi0[i] + tr, wi = a_wi0[i] + ts;
+      const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+      ra[SL][i] = *reinterpret_cast<const f32x4*>(ok ? p.x + a_base[i] + koff : p.zero);
+    }
+    tc += BK;
+    if (tc == p.C) {
+      tc = 0;
+      if (++ts == p.S) { ts = 0; ++tr; }
+    }
+#pragma unroll
+    for (int j = 0; j < PB; ++j)
+      rb[SL][j] = *reinterpret_cast<const u32x4*>(b_src[j] ? reinterpret_cast<const void*>(b_src[j] + step * BK)
+                                                           : reinterpret_cast<const void*>(p.zero));
+  };
+  auto store_tiles = [&](int buf, auto set) {
+    constexpr int SL = decltype(set)::value;
+    char* a = As + (buf * BM + row0) * BF16_PITCH + kc * 8;
+    char* b = Bs + (buf * BN + rowb) * BF16_PITCH + kb * 16;
+#pragma unroll
+    for (int i = 0; i < PA; ++i)
+      *reinterpret_cast<bf16x4*>(a + i * 32 * BF16_PITCH) = __builtin_convertvector(ra[SL][i], bf16x4);
+#pragma unroll
+    for (int j = 0; j < PB; ++j) *reinterpret_cast<u32x4*>(b + j * 64 * BF16_PITCH) = rb[SL][j];
+  };
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // fragment read offsets: lane (l&31) = row inside the 32x32 tile, (l>>5) selects k in {8h..8h+7} of a group of 16
+  const int frag = (lane & 31) * BF16_PITCH + 16 * (lane >> 5);
+  const int a_frag = (wr * TM * 32) * BF16_PITCH + frag;
+  const int b_frag = (wc * TN * 32) * BF16_PITCH + frag;
+
+  const int nsteps = p.ksteps;   // >= 1
+  load_tiles(0, Set0{});
+  if (DEPTH > 1 && nsteps > 1) load_tiles(1, Set1{});
+  if (DEPTH > 2 && nsteps > 2) load_tiles(2, Set2{});
+  if (DEPTH > 3 && nsteps > 3) load_tiles(3, Set3{});
+  store_tiles(0, Set0{});
+  if (nsteps > DEPTH) load_tiles(DEPTH, Set0{});
+  __syncthreads();
+  int cur = 0;
+  // one K-step; `set` = (s + 1) % DEPTH holds tile s + 1 and is refilled with tile s + 1 + DEPTH once that one is in LDS.
+  // STEADY: both exist - no conditions around the loads, so the compiler counts them and waits for the oldest set only.
+  auto kstep = [&](int s, auto set, auto steady) {
+    constexpr bool STEADY = decltype(steady)::value;
+    const char* Ab = As + cur * BM * BF16_PITCH + a_frag;
+    const char* Bb = Bs + cur * BN * BF16_PITCH + b_frag;
+    bf16x8 fa[2][TM], fb[2][TN];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i) fa[kk][i] = *reinterpret_cast<const bf16x8*>(Ab + i * 32 * BF16_PITCH + kk * 32);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) fb[kk][j] = *reinterpret_cast<const bf16x8*>(Bb + j * 32 * BF16_PITCH + kk * 32);
+    }
+    // operands are (weights, activations) as in mma_step: D col (lane) = pixel, D row (register) = channel
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kk][j], fa[kk][i], acc[i][j], 0, 0, 0);
+    if (STEADY || s + 1 < nsteps) store_tiles(cur ^ 1, set);   // stage cur^1 was last read before the previous step's barrier
+    if (STEADY || s + 1 + DEPTH < nsteps) load_tiles(s + 1 + DEPTH, set);
+    __syncthreads();
+    cur ^= 1;
+  };
+  // DEPTH consecutive steps from s, a multiple of DEPTH: step s + i refills the set of tile s + i + 1
+  auto round = [&](int s, auto steady) {
+    constexpr bool STEADY = decltype(steady)::value;
+    kstep(s, Set1{}, steady);
+    if (DEPTH > 1 && (STEADY || s + 1 < nsteps)) kstep(s + 1, Set2{}, steady);
+    if (DEPTH > 2 && (STEADY || s + 2 < nsteps)) kstep(s + 2, Set3{}, steady);
+    if (DEPTH > 3 && (STEADY || s + 3 < nsteps)) kstep(s + 3, Set0{}, steady);
+  };
+  int s = 0;
+  for (; s + 2 * DEPTH < nsteps; s += DEPTH) round(s, std::true_type{});
+  for (; s < nsteps; s += DEPTH) round(s, std::false_type{});
+
+  if (p.epi_lds && (p.K & 3) == 0)   // (uniform branch; every wave is past the K loop's last barrier and reads no LDS any more)
+    conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, p.M, smem + wave * 32 * LDS_PITCH, 0, 0);
+  else
+    conv_epilogue<TM, TN>(p, acc, m0, n0, wr, wc, lane, p.M, 0, 0);
+}
+
+// fp32 -> bf16, round to nearest even (the conversion the kernel applies to the activations)
+__global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, size_t count) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const __bf16 v = (__bf16)w[i];
+  out[i] = __builtin_bit_cast(unsigned short, v);
+}
+
+// The one analytic tile rule of the bf16 kernel: the 64x64 tile when 128x128 tiles would leave CUs without a workgroup
+bool bf16_small_tile(long M, int k) {
+  const int mode = g_bf16_tile;
+  if (mode) return mode == 1;
+  return ((M + 127) / 128) * ((k + 127) / 128) < NUM_CU;
+}
+
+template <int TM, int TN>
+int launch_bf16(ConvParams p, const unsigned short* wq, hipStream_t stream) {
+  constexpr int BM = 64 * TM, BN = 64 * TN;
+  constexpr size_t lds = (size_t)2 * (BM + BN) * BF16_PITCH;
+  p.tiles_m = (p.M + BM - 1) / BM;
+  p.tiles_n = (p.K + BN - 1) / BN;
+  constexpr int DEPTH = TM * TN == 1 ? 4 : 1;   // (see the kernel's staging ring)
+  return launch_kernel<conv_igemm_bf16<TM, TN, DEPTH>>("conv_igemm_bf16", 0, dim3(p.tiles_m * p.tiles_n), 256, lds, stream, p, wq);
+}
 }  // namespace
+
+extern "C" size_t frcnn_conv2d_pack_bf16_bytes(int k, int r, int s, int c) {
+  if (k <= 0 || r <= 0 || s <= 0 || c <= 0) return 0;
+  return (size_t)k * r * s * c * sizeof(unsigned short);
+}
+
+extern "C" int frcnn_conv2d_pack_bf16(const float* w_krsc, void* w_bf16, int k, int r, int s, int c, void* stream_) {
+  FRCNN_REQUIRE(w_krsc && w_bf16, "conv2d_pack_bf16: null tensor");
+  FRCNN_REQUIRE(k > 0 && r > 0 && s > 0 && c > 0, "conv2d_pack_bf16: bad shape k=%d r=%d s=%d c=%d", k, r, s, c);
+  const size_t count = (size_t)k * r * s * c;
+  FRCNN_REQUIRE((count + 255) / 256 < ((size_t)1 << 31), "conv2d_pack_bf16: filter too large");
+  return launch_kernel<pack_bf16_kernel>("pack_bf16_kernel", 2, dim3((unsigned)((count + 255) / 256)), 256, 0,
+                                         static_cast<hipStream_t>(stream_), w_krsc, static_cast<unsigned short*>(w_bf16), count);
+}
+
+extern "C" int frcnn_conv2d_bf16_set_tile(int mode) {
+  FRCNN_REQUIRE(mode >= 0 && mode <= 2, "conv2d_bf16_set_tile: mode %d (0 = by the number of workgroups, 1 = 64x64, 2 = 128x128)", mode);
+  g_bf16_tile = mode;
+  return FRCNN_OK;
+}
+
+extern "C" int frcnn_conv2d_fwd_bf16(const float* x, const void* w_bf16, const float* scale, const float* shift,
+                                     const float* residual, float* y, int n, int h, int w, int c, int k, int r, int s,
+                                     int stride, int pad, int relu, void* stream_) {
+  FRCNN_REQUIRE(x && w_bf16 && y, "conv2d_fwd_bf16: null tensor");
+  FRCNN_REQUIRE(conv_args_ok(n, h, w, c, k, r, s, stride, pad) && (c % BK) == 0,
+                "conv2d_fwd_bf16: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d (need c%%32==0)", n, h, w, c,
+                k, r, s, stride, pad);
+  FRCNN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_bf16)) & 15) == 0,
+                "conv2d_fwd_bf16: x and w_bf16 must be 16-byte aligned");
+  ConvParams p = {};
+  p.x = x; p.scale = scale; p.shift = shift; p.res = residual; p.y = y;
+  p.H = h; p.W = w; p.C = c; p.K = k; p.R = r; p.S = s; p.stride = stride; p.pad = pad;
+  p.Ho = (h + 2 * pad - r) / stride + 1;
+  p.Wo = (w + 2 * pad - s) / stride + 1;
+  const long M = (long)n * p.Ho * p.Wo;
+  FRCNN_REQUIRE(M * (long)k < (1L << 31) && (long)n * h * w * c < (1L << 31) && M + 128 < (1L << 31),
+                "conv2d_fwd_bf16: tensor too large for int32 indexing");
+  p.M = (int)M;
+  p.Ktot = r * s * c;
+  FRCNN_REQUIRE((long)k * p.Ktot < (1L << 31), "conv2d_fwd_bf16: filter too large for int32 indexing");
+  p.ksteps = p.Ktot / BK;
+  p.steps_per_split = p.ksteps;
+  p.relu = relu;
+  p.ys = 1;
+  p.grows[0] = p.grows[1] = p.grows[2] = p.grows[3] = p.M;
+  p.epi_lds = g_epi_lds;
+  p.zero = zero_page_address();
+  if (!p.zero) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv2d_fwd_bf16: cannot resolve the zero page's device address");
+  if (g_prof_on) ++g_prof_call;
+  const unsigned short* wq = static_cast<const unsigned short*>(w_bf16);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  return bf16_small_tile(M, k) ? launch_bf16<1, 1>(p, wq, stream) : launch_bf16<2, 2>(p, wq, stream);
+}
 
 extern "C" int frcnn_conv2d_fwd(const float* x, const float* wgt, const float* scale, const float* shift,
                                 const float* residual, float* y, int n, int h, int w, int c, int k, int r, int s,

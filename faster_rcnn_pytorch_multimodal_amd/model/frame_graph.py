@@ -158,7 +158,8 @@ class FrameRunner:
 # ---------------------------------------------------------------------------------------------------------------------
 def cfg_fingerprint(net):
     """Everything outside the frame's shape that a captured frame bakes in: proposal / NMS / pooling settings (the rotated
-    LiDAR NMS switch among them: a frame captured under one rule is never replayed under the other), the
+    LiDAR NMS switch and the bf16 convolution switch among them: a frame captured under one setting is never replayed under
+    the other), the
     uncertainty flags and sample counts, the process-wide kernel switches (the Python-level ones by value, the library's -
     forced tile, convolution algorithm / staging, RoIAlign and filter variants, memops mode, NMS tie rule - through
     ``frcnn_settings_signature``, a hash of their current values), the modules' train / eval state."""
@@ -169,7 +170,7 @@ def cfg_fingerprint(net):
                                                'EN_BBOX_EPISTEMIC_INV_TRANSFORM'))
     modes = tuple(m.training for m in net.modules())
     return (cfg.NET_TYPE, int(t.RPN_PRE_NMS_TOP_N), int(t.RPN_POST_NMS_TOP_N), float(t.RPN_NMS_THRESH), float(t.NMS_THRESH),
-            bool(t.get('NMS_ROTATED', False)),
+            bool(t.get('NMS_ROTATED', False)), bool(t.get('CONV_BF16', False)),
             str(t.get('MODE', 'nms')), int(t.get('RPN_TOP_N', 0)), str(cfg.POOLING_MODE), int(cfg.POOLING_SIZE),
             bool(cfg.ENABLE_CUSTOM_TAIL), uc, int(u.E_NUM_SAMPLE), int(u.A_NUM_CE_SAMPLE), ops.nms_suppress_at_equal(),
             ops._CONV_ALGO_MODE, ops._CONV_ALGO_FLAGS, bool(N.PROJECT_BEFORE_POOLING), bool(N.FUSE_PROJECTIONS),

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..model.config import cfg
 
 
 def pad4(c):
@@ -46,7 +47,7 @@ def stable_store(holder, name, key, fresh, refresh=None):
 
 # derived entries that read other derived entries (the KRSC filter) come second
 _REFRESH_ORDER = ('_frcnn_prepared', '_frcnn_perm', '_fused_cache', '_heads_cache', '_frcnn_wt', '_frcnn_winograd',
-                  '_frcnn_dgrad_winograd')
+                  '_frcnn_dgrad_winograd', '_bf16')
 
 
 def refresh_derived_weights(net):
@@ -120,7 +121,7 @@ def prepared_conv_concat(owner, cache_name, parts):
 
 
 def conv_bn_act(x, conv, bn=None, relu=False, residual=None, use_bn=True):
-    """NHWC in, NHWC out: act(bn(conv(x)) + residual) on the fp32 matrix cores."""
+    """NHWC in, NHWC out: act(bn(conv(x)) + residual) on the matrix cores (fp32; bf16 operands under cfg.TEST.CONV_BF16)."""
     if bn is not None and use_bn and bn.training:
         raise NotImplementedError("BatchNorm in training mode (batch statistics) is not on the HIP path yet")
     w, scale, shift = prepared_conv(conv, bn, use_bn)
@@ -128,11 +129,61 @@ def conv_bn_act(x, conv, bn=None, relu=False, residual=None, use_bn=True):
         x = ops.pad_channels(x, w.shape[-1])
     stride = conv.stride[0] if isinstance(conv.stride, (tuple, list)) else conv.stride
     pad = conv.padding[0] if isinstance(conv.padding, (tuple, list)) else conv.padding
+    return conv_forward(x, w, scale, shift, residual, conv, stride=stride, pad=pad, relu=relu, winograd_of=conv)
+
+
+# The mode of the Network.forward in progress ('TRAIN' / 'TEST'): frozen blocks of a training net are in eval() too, so
+# the modules' own state does not tell an inference frame from a training step.
+_NET_MODE = None
+
+
+def set_net_mode(mode):
+    global _NET_MODE
+    _NET_MODE = mode
+
+
+def conv_bf16_eligible(c, k, r, s, stride, pad, strided_out=False):
+    """Can ``ops.conv2d_nhwc_bf16`` run a convolution of this geometry?  (C % 32 == 0: a 32-wide reduction step lies inside
+    one filter tap; any k >= 1; no strided output.)"""
+    return (c > 0 and c % 32 == 0 and k >= 1 and r >= 1 and s >= 1 and stride >= 1 and pad >= 0 and not strided_out)
+
+
+def conv_bf16_wanted(x, w_krsc, stride, pad):
+    """cfg.TEST.CONV_BF16, a TEST-mode forward, no gradient wanted and an eligible layer."""
+    if not cfg.TEST.get('CONV_BF16', False) or _NET_MODE != 'TEST' or (torch.is_grad_enabled() and x.requires_grad):
+        return False
+    k, r, s, c = w_krsc.shape
+    return x.shape[-1] == c and conv_bf16_eligible(c, k, r, s, stride, pad)
+
+
+def _bf16_entry(holder, name, w_krsc):
+    """``w_krsc`` packed for ``ops.conv2d_nhwc_bf16``, cached on ``holder`` next to the fp32 filter it was made from and
+    re-packed IN PLACE when that filter changed (also the entry's refresh hook, after the filter's own).  A cache miss
+    inside a stream capture would launch the packing into the graph and pin a graph-pool tensor on the module: it raises
+    instead (run one eager frame first)."""
+    cache = holder.__dict__.get(name)
+    key = (w_krsc.data_ptr(), w_krsc._version, tuple(w_krsc.shape))
+    if cache is not None and cache[0] == key:
+        return cache[1][0]
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("bf16 filter of a %s layer is not prepared: run an eager frame before capturing" % (tuple(w_krsc.shape),))
+    return stable_store(holder, name, key, (ops.conv2d_pack_bf16(w_krsc),), refresh=lambda: _bf16_entry(holder, name, w_krsc))[0]
+
+
+def conv_forward(x, w_krsc, scale, shift, residual, holder, stride=1, pad=0, relu=False, winograd_of=None,
+                 cache_name='_frcnn_bf16'):
+    """The one forward convolution of the inference call sites.  With cfg.TEST.CONV_BF16 in a TEST-mode forward an eligible
+    layer (``conv_bf16_eligible``) runs ``ops.conv2d_nhwc_bf16`` on its packed filter, cached on ``holder`` under
+    ``cache_name``; every other call is ``ops.conv2d_nhwc`` exactly as without the switch (``winograd_of``: the module whose
+    pre-transformed Winograd filter a residual-free call may read)."""
+    if conv_bf16_wanted(x, w_krsc, stride, pad):
+        return ops.conv2d_nhwc_bf16(x, _bf16_entry(holder, cache_name, w_krsc), scale, shift, residual, stride=stride, pad=pad,
+                                    relu=relu)
     u = None
-    if residual is None:
+    if winograd_of is not None and residual is None:
         n, h, wd, c = x.shape
-        u = _winograd_filter(conv, w, (n, h, wd), stride, pad)
-    return ops.conv2d_nhwc(x, w, scale, shift, residual, stride=stride, pad=pad, relu=relu, w_winograd=u)
+        u = _winograd_filter(winograd_of, w_krsc, (n, h, wd), stride, pad)
+    return ops.conv2d_nhwc(x, w_krsc, scale, shift, residual, stride=stride, pad=pad, relu=relu, w_winograd=u)
 
 
 def _winograd_filter(conv, w_krsc, nhw, stride, pad):

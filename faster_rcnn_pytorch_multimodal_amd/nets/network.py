@@ -37,7 +37,7 @@ from . import autograd_ops
 from . import uncertainty
 from .autograd_ops import (_Holder, conv_bn_act_train, conv_on_patches_train, det_loss_train, fused_head_train, fused_head_weights, linear_train,
                            roi_align_train, rpn_loss_train, spatial_mean_train)
-from .hip_modules import conv_bn_act, pad4, prepared_conv, prepared_conv_concat, to_nchw_view, to_nhwc
+from .hip_modules import conv_bn_act, conv_forward, set_net_mode, pad4, prepared_conv, prepared_conv_concat, to_nchw_view, to_nhwc
 
 ROI_ALIGN_SAMPLING_RATIO = 0
 # inference runs layer4[0]'s input-side 1x1 convolutions on the feature map, before the RoIAlign (Network._layer4_projected);
@@ -223,7 +223,7 @@ class Network(nn.Module):
         rpn = conv_bn_act(net_conv_nhwc, self.rpn_net, None, relu=True)
         self._act_summaries['rpn'] = rpn
         w, b = self._fused_rpn_head()
-        return ops.conv2d_nhwc(rpn, w, None, b, None, stride=1, pad=0, relu=False)
+        return conv_forward(rpn, w, None, b, None, self, cache_name='_bf16_rpn_head')
 
     def _rpn_backward_on_labelled_pixels(self, hw):
         """Training: is the RPN's differentiable pass restricted to the pixels that carry a labelled anchor?  Possible for the
@@ -467,13 +467,13 @@ class Network(nn.Module):
         if FUSE_PROJECTIONS and w1.shape[0] % 256 == 0 and cfg.POOLING_SIZE == 7:
             wc, sc, bc = prepared_conv_concat(blk, '_fused_cache_l4proj', [(blk.conv1, blk.bn1, bn),
                                                                            (blk.downsample[0], blk.downsample[1], True)])
-            a1, identity = ops.roi_align_split(ops.conv2d_nhwc(x, wc), rois, cfg.POOLING_SIZE, scale, w1.shape[0],
+            a1, identity = ops.roi_align_split(conv_forward(x, wc, None, None, None, blk, cache_name='_bf16_l4proj'), rois, cfg.POOLING_SIZE, scale, w1.shape[0],
                                                ROI_ALIGN_SAMPLING_RATIO, roi_count=count, scale=sc, shift=bc, relu1=True,
                                                relu2=False)
         else:
-            a1 = ops.roi_align_nhwc(ops.conv2d_nhwc(x, w1), rois, cfg.POOLING_SIZE, scale, ROI_ALIGN_SAMPLING_RATIO,
+            a1 = ops.roi_align_nhwc(conv_forward(x, w1, None, None, None, blk.conv1), rois, cfg.POOLING_SIZE, scale, ROI_ALIGN_SAMPLING_RATIO,
                                     roi_count=count, scale=s1, shift=b1, relu=True)
-            identity = ops.roi_align_nhwc(ops.conv2d_nhwc(x, wd), rois, cfg.POOLING_SIZE, scale, ROI_ALIGN_SAMPLING_RATIO,
+            identity = ops.roi_align_nhwc(conv_forward(x, wd, None, None, None, blk.downsample[0]), rois, cfg.POOLING_SIZE, scale, ROI_ALIGN_SAMPLING_RATIO,
                                           roi_count=count, scale=sd, shift=bd, relu=False)
         out = conv_bn_act(a1, blk.conv2, blk.bn2, relu=True, use_bn=bn)
         y = conv_bn_act(out, blk.conv3, blk.bn3, relu=True, residual=identity, use_bn=bn)
@@ -591,6 +591,7 @@ class Network(nn.Module):
         # self._image is the NCHW-shaped view the reference exposes
         self._image = to_nchw_view(ops.pad_channels(image.contiguous(), pad4(image.shape[-1])))
         self._mode = mode
+        set_net_mode(mode)
         self._predictions = {}
         self._gt_boxes_dc = None
         if mode == 'TEST':

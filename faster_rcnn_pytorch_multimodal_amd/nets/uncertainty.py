@@ -28,7 +28,7 @@ import torch.nn as nn
 from .. import ops
 from ..model.config import cfg
 from .autograd_ops import (_BnTrainFn, _Holder, _param_grad_from_krsc, _transposed_filter, _wgrad, linear_train)
-from .hip_modules import pad4
+from .hip_modules import conv_forward, pad4
 
 # ---- reconstruction constants (the missing network.py) ---------------------------------------------------------------
 UC_FC1_DIVISOR = 2                 # *_fc1: fc7 -> fc7 / 2; *_fc2: fc7 / 2 -> _det_net_channels (= fc7 / 4)
@@ -151,7 +151,7 @@ def _linear(x2d, lin, bn=None, relu=False):
             raise NotImplementedError("BatchNorm1d of the uncertainty heads in train() mode at test time")
         scale = (bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)).contiguous()
         shift = (bn.bias.detach() - bn.running_mean.detach() * scale + lin.bias.detach() * scale).contiguous()
-    return ops.conv2d_nhwc(x2d.contiguous().view(n, 1, 1, c), w.contiguous(), scale, shift, None, relu=relu).view(n, -1)
+    return conv_forward(x2d.contiguous().view(n, 1, 1, c), w.contiguous(), scale, shift, None, lin, relu=relu).view(n, -1)
 
 
 def _branch(net, prefix, fc7, epistemic, samples, seed, seed_dev=None):

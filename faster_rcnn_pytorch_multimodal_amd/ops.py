@@ -207,6 +207,73 @@ def conv2d_nhwc(x, w_krsc, scale=None, shift=None, residual=None, stride=1, pad=
     return out
 
 
+def conv2d_pack_bf16(w_krsc):
+    """(K,R,S,C) fp32 filter -> the same array as bf16 words (int16 tensor), rounded to nearest even: the filter operand of
+    ``conv2d_nhwc_bf16`` (frcnn_conv2d_pack_bf16); constant while the weights are."""
+    _dev_f32(w_krsc, "w")
+    if w_krsc.dim() != 4:
+        raise _hip.HipError("conv2d_pack_bf16: need a (k,r,s,c) filter, got shape %s" % (tuple(w_krsc.shape),))
+    lib = _hip.load()
+    k, r, s, c = w_krsc.shape
+    out = torch.empty((k, r, s, c), dtype=torch.int16, device=w_krsc.device)
+    _hip.check(lib.frcnn_conv2d_pack_bf16(_ptr(w_krsc), _ptr(out), k, r, s, c, _stream()), "frcnn_conv2d_pack_bf16")
+    return out
+
+
+def set_conv_bf16_tile(mode):
+    """Test / timing hook of ``conv2d_nhwc_bf16``: 0 = the library's rule, 1 = 64x64 tiles, 2 = 128x128 tiles
+    (frcnn_conv2d_bf16_set_tile); the results do not depend on it."""
+    _hip.check(_hip.load().frcnn_conv2d_bf16_set_tile(int(mode)), "frcnn_conv2d_bf16_set_tile")
+
+
+def conv2d_nhwc_bf16(x, w_bf16, scale=None, shift=None, residual=None, stride=1, pad=0, relu=False, out=None):
+    """y = act(conv(bf16(x), w_bf16) * scale + shift + residual) with fp32 accumulation  —  frcnn_conv2d_fwd_bf16.  x, scale,
+    shift, residual and y are fp32 as for ``conv2d_nhwc``; ``w_bf16`` comes from ``conv2d_pack_bf16``.  Needs C % 32 == 0."""
+    _dev_f32(x, "x")
+    if not isinstance(w_bf16, torch.Tensor) or not w_bf16.is_cuda:
+        raise _hip.HipError("w_bf16 must be a tensor on the MI355X (got %s); this package has no CPU path"
+                            % (getattr(w_bf16, "device", type(w_bf16)),))
+    if w_bf16.dtype != torch.int16 or not w_bf16.is_contiguous() or w_bf16.dim() != 4:
+        raise _hip.HipError("w_bf16 must be a contiguous (k,r,s,c) int16 tensor of bf16 words (conv2d_pack_bf16), got %s %s"
+                            % (w_bf16.dtype, tuple(w_bf16.shape)))
+    if x.dim() != 4:
+        raise _hip.HipError("conv2d_nhwc_bf16: x must be (n,h,w,c), got shape %s" % (tuple(x.shape),))
+    n, h, w, c = x.shape
+    k, r, s, c2 = w_bf16.shape
+    if c2 != c:
+        raise _hip.HipError("conv2d_nhwc_bf16: input has %d channels, filter expects %d" % (c, c2))
+    if c % 32 != 0:
+        raise _hip.HipError("conv2d_nhwc_bf16: needs c %% 32 == 0, got c = %d" % c)
+    stride, pad = int(stride), int(pad)
+    if stride < 1 or pad < 0 or h + 2 * pad < r or w + 2 * pad < s:
+        raise _hip.HipError("conv2d_nhwc_bf16: bad geometry h=%d w=%d r=%d s=%d stride=%d pad=%d" % (h, w, r, s, stride, pad))
+    for nm, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _dev_f32(t, nm)
+            if t.numel() != k:
+                raise _hip.HipError("conv2d_nhwc_bf16: %s has %d elements, expected %d" % (nm, t.numel(), k))
+    ho, wo = conv_out_hw(h, w, r, s, stride, pad)
+    if out is None:
+        out = torch.empty((n, ho, wo, k), dtype=torch.float32, device=x.device)
+    else:
+        _dev_f32(out, "out")
+        if tuple(out.shape) != (n, ho, wo, k):
+            raise _hip.HipError("conv2d_nhwc_bf16: out has shape %s, expected %s" % (tuple(out.shape), (n, ho, wo, k)))
+    if residual is not None:
+        _dev_f32(residual, "residual")
+        if tuple(residual.shape) != (n, ho, wo, k):
+            raise _hip.HipError("conv2d_nhwc_bf16: residual shape %s != output shape %s" % (tuple(residual.shape), (n, ho, wo, k)))
+    _hip.check(_hip.load().frcnn_conv2d_fwd_bf16(_ptr(x), _ptr(w_bf16), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(out), n, h,
+                                                 w, c, k, r, s, stride, pad, int(bool(relu)), _stream()), "frcnn_conv2d_fwd_bf16")
+    if PROFILE is not None:
+        PROFILE.append({"n": n, "h": h, "w": w, "c": c, "k": k, "r": r, "s": s, "stride": stride, "pad": pad,
+                        "residual": residual is not None, "relu": bool(relu), "flops": 2.0 * n * ho * wo * k * r * s * c,
+                        "bf16": True})
+    if FLOPS is not None:
+        _log_flops('fwd', 2.0 * n * ho * wo * k * r * s * c)
+    return out
+
+
 def winograd_eligible(k, r, s, c, stride, pad):
     """The layers frcnn_conv2d_set_algo's Winograd F(2x2, 3x3) form applies to (no residual operand)."""
     return r == 3 and s == 3 and stride == 1 and pad == 1 and c % 4 == 0 and k % 4 == 0

@@ -37,7 +37,8 @@ int frcnn_version(void);
 int frcnn_set_memops_mode(int mode);
 int frcnn_get_memops_mode(void);
 /* Hash of the CURRENT VALUES of every process-wide switch that selects kernels (frcnn_set_memops_mode, frcnn_conv2d_set_tile /
- * _set_algo / _set_staging, frcnn_roi_align_set_variant, frcnn_filter_set_variant, frcnn_nms_set_suppress_at_equal): a caller
+ * _set_algo / _set_staging / frcnn_conv2d_bf16_set_tile, frcnn_roi_align_set_variant, frcnn_filter_set_variant,
+ * frcnn_nms_set_suppress_at_equal; a bf16 tile mode of 0 leaves the hash as it was without that switch): a caller
  * that holds captured hipGraphs of entry points of this library (the reference's per-frame loop lib/model/test.py:183-228
  * replayed by model/frame_graph.FramePool) keys its captures by it - another value means the captures describe other kernels. */
 unsigned frcnn_settings_signature(void);
@@ -209,6 +210,22 @@ int frcnn_conv2d_winograd_filter(const float* w_krsc, float* u, int k, int c, vo
 int frcnn_conv2d_fwd_pre(const float* x, const float* w_krsc, const float* w_winograd, const float* scale,
                          const float* shift, const float* residual, float* y, int n, int h, int w, int c, int k, int r,
                          int s, int stride, int pad, int relu, int split_k, void* ws, size_t ws_bytes, void* stream);
+
+/* Opt-in inference form of frcnn_conv2d_fwd with bf16 OPERANDS on v_mfma_f32_32x32x16_bf16 (fp32 accumulation):
+ *     y = act( (sum bf16(x) * bf16(w)) * scale + shift + residual )
+ * x, scale, shift, residual and y are fp32 exactly as for frcnn_conv2d_fwd; x is rounded to bf16 (nearest even) inside the
+ * kernel.  w_bf16 is the filter packed once per weight version by frcnn_conv2d_pack_bf16: a plain (k,r,s,c) array of 16-bit
+ * words, fp32 -> bf16 round to nearest even (+-0 and +-inf kept, NaN stays NaN), frcnn_conv2d_pack_bf16_bytes bytes.
+ * Needs c % 32 == 0 (else FRCNN_ERR_ARG) and 16-byte aligned x / w_bf16; any k >= 1.  No split-K, no Winograd, no workspace,
+ * no plan-cache entry: one implicit-GEMM launch on a 128x128 tile, or on a 64x64 tile when 128x128 tiles would number fewer
+ * than the CUs.  Both tiles give bit-identical results.  frcnn_conv2d_bf16_set_tile is a test / timing hook: 0 = that rule,
+ * 1 = 64x64, 2 = 128x128. */
+size_t frcnn_conv2d_pack_bf16_bytes(int k, int r, int s, int c);
+int frcnn_conv2d_pack_bf16(const float* w_krsc, void* w_bf16, int k, int r, int s, int c, void* stream);
+int frcnn_conv2d_fwd_bf16(const float* x, const void* w_bf16, const float* scale, const float* shift,
+                          const float* residual, float* y, int n, int h, int w, int c, int k, int r, int s, int stride,
+                          int pad, int relu, void* stream);
+int frcnn_conv2d_bf16_set_tile(int mode);
 
 /* nn.MaxPool2d(kernel_size=3, stride=2, padding=1)  (lib/nets/resnet.py:156), NHWC. */
 int frcnn_maxpool3x3s2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
