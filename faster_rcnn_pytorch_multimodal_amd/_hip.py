@@ -28,6 +28,11 @@ PROTOTYPES = {
     "frcnn_conv2d_pack_bf16": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_conv2d_fwd_bf16": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 10 + [_P]),
     "frcnn_conv2d_bf16_set_tile": (c_int, [c_int]),
+    "frcnn_conv2d_pack_bf16x3_bytes": (c_size_t, [c_int] * 4),
+    "frcnn_conv2d_pack_bf16x3": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "frcnn_conv2d_fwd_bf16x3": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 10 + [_P]),
+    "frcnn_conv2d_split_bf16_wanted": (c_int, [c_int] * 9),
+    "frcnn_conv2d_split_bf16_enable": (c_int, [c_int]),
     "frcnn_conv2d_set_tile": (c_int, [c_int, c_int]),
     "frcnn_conv2d_set_staging": (c_int, [c_int]),
     "frcnn_conv2d_set_algo": (c_int, [c_int]),

@@ -1561,6 +1561,8 @@ bool lookup_plan(const ShapeKey& key, Plan* pl) {
 std::atomic<int> g_use_dma{1};
 // test / timing hook (frcnn_conv2d_bf16_set_tile): 0 = bf16_small_tile's rule, 1 = 64x64, 2 = 128x128
 std::atomic<int> g_bf16_tile{0};
+// test hook (frcnn_conv2d_split_bf16_enable): 0 = frcnn_conv2d_split_bf16_wanted answers 0 everywhere
+std::atomic<int> g_split_bf16{1};
 
 bool conv_args_ok(int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
   return n > 0 && h > 0 && w > 0 && c > 0 && (c % 4) == 0 && k > 0 && r > 0 && s > 0 && stride > 0 && pad >= 0 &&
@@ -1653,7 +1655,7 @@ unsigned long long frcnn::conv_settings_word() {
          ((unsigned long long)(g_wino_trim.load() ? 0 : 1) << 6) |
          ((unsigned long long)g_epi_lds.load() << 8) | ((unsigned long long)g_use_dma.load() << 12) |
          ((unsigned long long)g_force_tm.load() << 16) | ((unsigned long long)g_force_tn.load() << 24) |
-         ((unsigned long long)g_bf16_tile.load() << 32);
+         ((unsigned long long)g_bf16_tile.load() << 32) | ((unsigned long long)(g_split_bf16.load() ? 0 : 1) << 36);
 }
 
 extern "C" int frcnn_conv2d_clear_plans(void) {
@@ -2254,18 +2256,28 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // eight packed bf16 in flight between the global load and the LDS store
 constexpr int BF16_PITCH = 80;   // bytes per LDS row (32 bf16 + 16 B pad)
+// split form: (activation plane, filter plane) of the six products of a k-group in issue order; 0 = hi, 1 = mid, 2 = lo.
+// The three left out (mid*lo, lo*mid, lo*lo) are at most 2^-26 of the product.  The first five (at most 2^-8 of hi*hi) are
+// summed in an accumulator of their own and added to the hi*hi accumulator once, after the K loop: the MFMA aligns its
+// addends to the largest one and cuts what falls below, so small products added straight into the large sum lose their
+// low bits at every instruction - measured, 1.15 to 2 times the fp32 kernel's error and a bias of its own
+// (profiles/conv_split_bf16.md); apart, the result carries the hi*hi chain's error only, 0.34 to 0.70 of the fp32 kernel's.
+constexpr int kSplitTerms[6][2] = {{2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
 
-template <int TM, int TN, int DEPTH>
-__global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const ConvParams p, const unsigned short* __restrict__ wq) {
+// NP = 3 is the split form (frcnn_conv2d_fwd_bf16x3, see below the kernel): three bf16 planes per operand.
+template <int TM, int TN, int DEPTH, int NP>
+__global__ __launch_bounds__(256, (NP == 3 && TM * TN > 1) ? 1 : 2) void conv_igemm_bf16(const ConvParams p, const unsigned short* __restrict__ wq) {
   static_assert(DEPTH >= 1 && DEPTH <= 4, "register sets of the staging ring");
+  static_assert(NP == 1 || NP == 3, "one bf16 plane per operand, or hi / mid / lo");
   constexpr int WN = 2;
   constexpr int BM = 64 * TM, BN = 64 * TN;
   constexpr int PA = BM / 32;   // A: 8 threads x 4 floats cover a row's K-step, 32 rows per pass
   constexpr int PB = BN / 64;   // B: 4 threads x 8 bf16 cover a row's K-step, 64 rows per pass
   static_assert(2 * (BM + BN) * BF16_PITCH >= 4 * 32 * LDS_PITCH * (int)sizeof(float), "the epilogue's patches fit the stages");
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* const As = reinterpret_cast<char*>(smem);   // [2][BM][80 B]
-  char* const Bs = As + 2 * BM * BF16_PITCH;        // [2][BN][80 B]
+  char* const As = reinterpret_cast<char*>(smem);   // [2][NP][BM][80 B]
+  char* const Bs = As + 2 * NP * BM * BF16_PITCH;   // [2][NP][BN][80 B]
+  const size_t w_plane = (size_t)p.K * p.Ktot;      // NP == 3: the filter's planes are whole KRSC arrays, hi then mid then lo
 
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
@@ -2304,7 +2316,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const ConvParams p, co
   // same tile: with one tile ahead a lone 64x64 workgroup pays the HBM / L2 latency once per K-step (DEPTH = 4 there); the
   // 128x128 tile keeps one set - 154 VGPRs, three workgroups per CU - because a deeper ring costs it the third workgroup.
   f32x4 ra[DEPTH][PA];
-  u32x4 rb[DEPTH][PB];
+  u32x4 rb[DEPTH][PB * NP];
   typedef std::integral_constant<int, 0> Set0;
   typedef std::integral_constant<int, 1 % DEPTH> Set1;   // SetN: the set of tile N
   typedef std::integral_constant<int, 2 % DEPTH> Set2;
@@ -2327,18 +2339,31 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const ConvParams p, co
     }
 #pragma unroll
     for (int j = 0; j < PB; ++j)
-      rb[SL][j] = *reinterpret_cast<const u32x4*>(b_src[j] ? reinterpret_cast<const void*>(b_src[j] + step * BK)
-                                                           : reinterpret_cast<const void*>(p.zero));
+#pragma unroll
+      for (int q = 0; q < NP; ++q)
+        rb[SL][j * NP + q] = *reinterpret_cast<const u32x4*>(b_src[j] ? reinterpret_cast<const void*>(b_src[j] + q * w_plane + step * BK)
+                                                                      : reinterpret_cast<const void*>(p.zero));
   };
   auto store_tiles = [&](int buf, auto set) {
     constexpr int SL = decltype(set)::value;
-    char* a = As + (buf * BM + row0) * BF16_PITCH + kc * 8;
-    char* b = Bs + (buf * BN + rowb) * BF16_PITCH + kb * 16;
+    char* a = As + (buf * NP * BM + row0) * BF16_PITCH + kc * 8;
+    char* b = Bs + (buf * NP * BN + rowb) * BF16_PITCH + kb * 16;
 #pragma unroll
-    for (int i = 0; i < PA; ++i)
-      *reinterpret_cast<bf16x4*>(a + i * 32 * BF16_PITCH) = __builtin_convertvector(ra[SL][i], bf16x4);
+    for (int i = 0; i < PA; ++i) {
+      const bf16x4 hi = __builtin_convertvector(ra[SL][i], bf16x4);
+      *reinterpret_cast<bf16x4*>(a + i * 32 * BF16_PITCH) = hi;
+      if constexpr (NP == 3) {   // split_bf16x3's chain, once per tile element: both remainders are exact in fp32
+        const f32x4 r1 = ra[SL][i] - __builtin_convertvector(hi, f32x4);
+        const bf16x4 mid = __builtin_convertvector(r1, bf16x4);
+        const f32x4 r2 = r1 - __builtin_convertvector(mid, f32x4);
+        *reinterpret_cast<bf16x4*>(a + (BM + i * 32) * BF16_PITCH) = mid;
+        *reinterpret_cast<bf16x4*>(a + (2 * BM + i * 32) * BF16_PITCH) = __builtin_convertvector(r2, bf16x4);
+      }
+    }
 #pragma unroll
-    for (int j = 0; j < PB; ++j) *reinterpret_cast<u32x4*>(b + j * 64 * BF16_PITCH) = rb[SL][j];
+    for (int j = 0; j < PB; ++j)
+#pragma unroll
+      for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(b + (q * BN + j * 64) * BF16_PITCH) = rb[SL][j * NP + q];
   };
 
   f32x16 acc[TM][TN];
@@ -2348,6 +2373,16 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const ConvParams p, co
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  // split form: the five small products of every k-group go to an accumulator of their own (see kSplitTerms)
+  f32x16 low[TM][TN];   // (unused, and removed by the compiler, when NP == 1)
+  if constexpr (NP == 3) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) low[i][j][r] = 0.f;
+  }
 
   // fragment read offsets: lane (l&31) = row inside the 32x32 tile, (l>>5) selects k in {8h..8h+7} of a group of 16
   const int frag = (lane & 31) * BF16_PITCH + 16 * (lane >> 5);
@@ -2363,28 +2398,65 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const ConvParams p, co
   if (nsteps > DEPTH) load_tiles(DEPTH, Set0{});
   __syncthreads();
   int cur = 0;
+  // split form only: the fragments of a step's two k-groups, three planes per operand
+  bf16x8 ga[2][TM][NP], gb[2][TN][NP];
+  auto read_frags = [&](int stage, int kk, auto which) {
+    constexpr int G = decltype(which)::value;
+    const char* Ab = As + stage * NP * BM * BF16_PITCH + a_frag + kk * 32;
+    const char* Bb = Bs + stage * NP * BN * BF16_PITCH + b_frag + kk * 32;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i) ga[G][i][q] = *reinterpret_cast<const bf16x8*>(Ab + (q * BM + i * 32) * BF16_PITCH);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) gb[G][j][q] = *reinterpret_cast<const bf16x8*>(Bb + (q * BN + j * 32) * BF16_PITCH);
+    }
+  };
+  // a k = 16 group: six products in kSplitTerms' order, the five small ones into `low`, hi*hi into `acc`; consecutive MFMAs
+  // go to different outputs' accumulators, each accumulator sees its terms in this order and the groups in ascending k.
+  // (A generic lambda: instantiated only where it is called, under NP == 3.  On the 64x64 tile, TM = TN = 1, the five
+  // `low` MFMAs of a group depend on each other back to back; the rule never gives that tile a layer of the frame.)
+  auto mma_group = [&](auto which) {
+    constexpr int G = decltype(which)::value;
+#pragma unroll
+    for (int term = 0; term < 6; ++term)
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          f32x16& to = term < 5 ? low[i][j] : acc[i][j];
+          to = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gb[G][j][kSplitTerms[term][1]], ga[G][i][kSplitTerms[term][0]], to, 0, 0, 0);
+        }
+  };
   // one K-step; `set` = (s + 1) % DEPTH holds tile s + 1 and is refilled with tile s + 1 + DEPTH once that one is in LDS.
   // STEADY: both exist - no conditions around the loads, so the compiler counts them and waits for the oldest set only.
   auto kstep = [&](int s, auto set, auto steady) {
     constexpr bool STEADY = decltype(steady)::value;
-    const char* Ab = As + cur * BM * BF16_PITCH + a_frag;
-    const char* Bb = Bs + cur * BN * BF16_PITCH + b_frag;
-    bf16x8 fa[2][TM], fb[2][TN];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) fa[kk][i] = *reinterpret_cast<const bf16x8*>(Ab + i * 32 * BF16_PITCH + kk * 32);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[kk][j] = *reinterpret_cast<const bf16x8*>(Bb + j * 32 * BF16_PITCH + kk * 32);
-    }
     // operands are (weights, activations) as in mma_step: D col (lane) = pixel, D row (register) = channel
+    if constexpr (NP == 1) {
+      const char* Ab = As + cur * BM * BF16_PITCH + a_frag;
+      const char* Bb = Bs + cur * BN * BF16_PITCH + b_frag;
+      bf16x8 fa[2][TM], fb[2][TN];
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
+      for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i) fa[kk][i] = *reinterpret_cast<const bf16x8*>(Ab + i * 32 * BF16_PITCH + kk * 32);
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kk][j], fa[kk][i], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < TN; ++j) fb[kk][j] = *reinterpret_cast<const bf16x8*>(Bb + j * 32 * BF16_PITCH + kk * 32);
+      }
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kk][j], fa[kk][i], acc[i][j], 0, 0, 0);
+    } else {
+      read_frags(cur, 0, std::integral_constant<int, 0>{});
+      read_frags(cur, 1, std::integral_constant<int, 1>{});
+      mma_group(std::integral_constant<int, 0>{});
+      mma_group(std::integral_constant<int, 1>{});
+    }
     if (STEADY || s + 1 < nsteps) store_tiles(cur ^ 1, set);   // stage cur^1 was last read before the previous step's barrier
     if (STEADY || s + 1 + DEPTH < nsteps) load_tiles(s + 1 + DEPTH, set);
     __syncthreads();
@@ -2402,6 +2474,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const ConvParams p, co
   for (; s + 2 * DEPTH < nsteps; s += DEPTH) round(s, std::true_type{});
   for (; s < nsteps; s += DEPTH) round(s, std::false_type{});
 
+  if constexpr (NP == 3) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] += low[i][j];
+  }
   if (p.epi_lds && (p.K & 3) == 0)   // (uniform branch; every wave is past the K loop's last barrier and reads no LDS any more)
     conv_epilogue_lds<TM, TN>(p, acc, m0, n0, wr, wc, lane, p.M, smem + wave * 32 * LDS_PITCH, 0, 0);
   else
@@ -2423,15 +2501,36 @@ bool bf16_small_tile(long M, int k) {
   return ((M + 127) / 128) * ((k + 127) / 128) < NUM_CU;
 }
 
-template <int TM, int TN>
+// Split form of pack_bf16_kernel: hi = bf16(w), mid = bf16(w - hi), lo = bf16(w - hi - mid), each rounded to nearest even;
+// both remainders are exact in fp32 and hi + mid + lo == w for finite w whose remainders do not underflow.
+__global__ __launch_bounds__(256) void pack_bf16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, size_t count) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const float v = w[i];
+  const __bf16 hi = (__bf16)v;
+  const float r1 = v - (float)hi;
+  const __bf16 mid = (__bf16)r1;
+  const __bf16 lo = (__bf16)(r1 - (float)mid);
+  out[i] = __builtin_bit_cast(unsigned short, hi);
+  out[count + i] = __builtin_bit_cast(unsigned short, mid);
+  out[2 * count + i] = __builtin_bit_cast(unsigned short, lo);
+}
+
+// LDS of a workgroup: two stages x NP planes x (BM + BN) rows of 80 B.  NP = 3: 60 KB on the 64x64 tile (two workgroups
+// per CU, the staging ring stays four deep) and 120 KB on the 128x128 tile - one workgroup per CU, so the kernel is built
+// for one wave per SIMD (512 registers) and keeps two tiles in flight.
+template <int TM, int TN, int NP>
 int launch_bf16(ConvParams p, const unsigned short* wq, hipStream_t stream) {
   constexpr int BM = 64 * TM, BN = 64 * TN;
-  constexpr size_t lds = (size_t)2 * (BM + BN) * BF16_PITCH;
+  constexpr size_t lds = (size_t)2 * NP * (BM + BN) * BF16_PITCH;
+  static_assert(lds <= 160 * 1024, "LDS of a gfx950 CU");
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.K + BN - 1) / BN;
-  constexpr int DEPTH = TM * TN == 1 ? 4 : 1;   // (see the kernel's staging ring)
-  return launch_kernel<conv_igemm_bf16<TM, TN, DEPTH>>("conv_igemm_bf16", 0, dim3(p.tiles_m * p.tiles_n), 256, lds, stream, p, wq);
+  constexpr int DEPTH = TM * TN == 1 ? 4 : (NP == 3 ? 2 : 1);   // (see the kernel's staging ring)
+  return launch_kernel<conv_igemm_bf16<TM, TN, DEPTH, NP>>(NP == 3 ? "conv_igemm_bf16x3" : "conv_igemm_bf16", 0, dim3(p.tiles_m * p.tiles_n),
+                                                           256, lds, stream, p, wq);
 }
+
 }  // namespace
 
 extern "C" size_t frcnn_conv2d_pack_bf16_bytes(int k, int r, int s, int c) {
@@ -2454,9 +2553,10 @@ extern "C" int frcnn_conv2d_bf16_set_tile(int mode) {
   return FRCNN_OK;
 }
 
-extern "C" int frcnn_conv2d_fwd_bf16(const float* x, const void* w_bf16, const float* scale, const float* shift,
-                                     const float* residual, float* y, int n, int h, int w, int c, int k, int r, int s,
-                                     int stride, int pad, int relu, void* stream_) {
+namespace {
+template <int NP>
+int fwd_bf16(const float* x, const void* w_bf16, const float* scale, const float* shift, const float* residual, float* y, int n,
+             int h, int w, int c, int k, int r, int s, int stride, int pad, int relu, void* stream_) {
   FRCNN_REQUIRE(x && w_bf16 && y, "conv2d_fwd_bf16: null tensor");
   FRCNN_REQUIRE(conv_args_ok(n, h, w, c, k, r, s, stride, pad) && (c % BK) == 0,
                 "conv2d_fwd_bf16: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d (need c%%32==0)", n, h, w, c,
@@ -2485,7 +2585,51 @@ extern "C" int frcnn_conv2d_fwd_bf16(const float* x, const void* w_bf16, const f
   if (g_prof_on) ++g_prof_call;
   const unsigned short* wq = static_cast<const unsigned short*>(w_bf16);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  return bf16_small_tile(M, k) ? launch_bf16<1, 1>(p, wq, stream) : launch_bf16<2, 2>(p, wq, stream);
+  return bf16_small_tile(M, k) ? launch_bf16<1, 1, NP>(p, wq, stream) : launch_bf16<2, 2, NP>(p, wq, stream);
+}
+}  // namespace
+
+extern "C" int frcnn_conv2d_fwd_bf16(const float* x, const void* w_bf16, const float* scale, const float* shift,
+                                     const float* residual, float* y, int n, int h, int w, int c, int k, int r, int s,
+                                     int stride, int pad, int relu, void* stream_) {
+  return fwd_bf16<1>(x, w_bf16, scale, shift, residual, y, n, h, w, c, k, r, s, stride, pad, relu, stream_);
+}
+
+extern "C" int frcnn_conv2d_fwd_bf16x3(const float* x, const void* w_bf16x3, const float* scale, const float* shift,
+                                       const float* residual, float* y, int n, int h, int w, int c, int k, int r, int s,
+                                       int stride, int pad, int relu, void* stream_) {
+  return fwd_bf16<3>(x, w_bf16x3, scale, shift, residual, y, n, h, w, c, k, r, s, stride, pad, relu, stream_);
+}
+
+extern "C" size_t frcnn_conv2d_pack_bf16x3_bytes(int k, int r, int s, int c) { return 3 * frcnn_conv2d_pack_bf16_bytes(k, r, s, c); }
+
+extern "C" int frcnn_conv2d_pack_bf16x3(const float* w_krsc, void* w_bf16x3, int k, int r, int s, int c, void* stream_) {
+  FRCNN_REQUIRE(w_krsc && w_bf16x3, "conv2d_pack_bf16x3: null tensor");
+  FRCNN_REQUIRE(k > 0 && r > 0 && s > 0 && c > 0, "conv2d_pack_bf16x3: bad shape k=%d r=%d s=%d c=%d", k, r, s, c);
+  const size_t count = (size_t)k * r * s * c;
+  FRCNN_REQUIRE((count + 255) / 256 < ((size_t)1 << 31), "conv2d_pack_bf16x3: filter too large");
+  return launch_kernel<pack_bf16x3_kernel>("pack_bf16x3_kernel", 2, dim3((unsigned)((count + 255) / 256)), 256, 0,
+                                           static_cast<hipStream_t>(stream_), w_krsc, static_cast<unsigned short*>(w_bf16x3), count);
+}
+
+extern "C" int frcnn_conv2d_split_bf16_enable(int on) {
+  FRCNN_REQUIRE(on == 0 || on == 1, "conv2d_split_bf16_enable: %d (0 or 1)", on);
+  g_split_bf16 = on;
+  return FRCNN_OK;
+}
+
+// The rule, in the GEMM's dimensions M = n*ho*wo, N = k, Ktot = r*s*c (profiles/conv_split_bf16.md): the split kernel
+// replaces the fp32 plan where its 128x128 tile applies (at least one workgroup per CU) and the GEMM is long enough in
+// both N and Ktot for six bf16 MFMAs per fragment pair to outrun the fp32 pipe - except where fp32 has a Winograd form,
+// which measured faster than the split direct convolution.  0 while a hook pins the fp32 kernels.
+extern "C" int frcnn_conv2d_split_bf16_wanted(int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
+  // every hook that picks among the fp32 kernels keeps its meaning: forced tile, algorithm mode and flags, staging
+  if (!g_split_bf16 || g_force_tm != 0 || g_algo_mode != 0 || g_wino_fuse != 1 || g_epi_lds != 1 || g_wino_trim != 1 || g_use_dma != 1) return 0;
+  if (!conv_args_ok(n, h, w, c, k, r, s, stride, pad) || (c % BK) != 0) return 0;
+  const long M = (long)n * ((h + 2 * pad - r) / stride + 1) * ((w + 2 * pad - s) / stride + 1);
+  const long ktot = (long)r * s * c;
+  if (winograd_ok(r, s, stride, pad, c, k, 1)) return 0;   // F(2x2, 3x3) multiplies 2.25 times less: measured faster in fp32
+  return ((M + 127) / 128) * ((k + 127) / 128) >= NUM_CU && k >= 512 && ktot >= 512;
 }
 
 extern "C" int frcnn_conv2d_fwd(const float* x, const float* wgt, const float* scale, const float* shift,

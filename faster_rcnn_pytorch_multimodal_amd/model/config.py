@@ -77,6 +77,7 @@ def _defaults():
                   FRAME_GRAPHS=True,       # replay each frame as a captured hipGraph (False: eager launches)
                   NMS_ROTATED=False,       # not in the reference (its filter_predictions.py:56-57 is commented out), LiDAR only: suppress on the rotated BEV footprints (utils/bbox.nms_rotated_host) instead of filter_predictions.py:55-67's yaw-less rectangles
                   CONV_BF16=False,         # not in the reference: TEST-mode convolutions with C % 32 == 0 round their operands to bf16 and run on v_mfma_f32_32x32x16_bf16 (fp32 accumulation, fp32 activations in memory; nets/hip_modules.conv_forward).  Changes the results (profiles/conv_bf16.md); training ignores it
+                  CONV_SPLIT_BF16=True,    # not in the reference: TEST-mode convolutions the library's rule selects (frcnn_conv2d_split_bf16_wanted: the large layer4 / projection GEMMs) run as fp32-accurate split-bf16 GEMMs - each operand as three bf16 planes, six products per k-group (nets/hip_modules.conv_forward, profiles/conv_split_bf16.md).  CONV_BF16 takes precedence; training ignores it
                   FRAMES_IN_FLIGHT=4,      # test_net: frames in flight, one HIP stream each
                   GRAPH_MAX_SHAPES=4,      # distinct frame problems held as graphs (least recently used one is dropped)
                   GRAPH_AUTOTUNE=True)     # time the convolution plans of a new frame shape during its warm-up frames

@@ -158,7 +158,7 @@ class FrameRunner:
 # ---------------------------------------------------------------------------------------------------------------------
 def cfg_fingerprint(net):
     """Everything outside the frame's shape that a captured frame bakes in: proposal / NMS / pooling settings (the rotated
-    LiDAR NMS switch and the bf16 convolution switch among them: a frame captured under one setting is never replayed under
+    LiDAR NMS switch and the two bf16 convolution switches (CONV_BF16, CONV_SPLIT_BF16) among them: a frame captured under one setting is never replayed under
     the other), the
     uncertainty flags and sample counts, the process-wide kernel switches (the Python-level ones by value, the library's -
     forced tile, convolution algorithm / staging, RoIAlign and filter variants, memops mode, NMS tie rule - through
@@ -170,7 +170,7 @@ def cfg_fingerprint(net):
                                                'EN_BBOX_EPISTEMIC_INV_TRANSFORM'))
     modes = tuple(m.training for m in net.modules())
     return (cfg.NET_TYPE, int(t.RPN_PRE_NMS_TOP_N), int(t.RPN_POST_NMS_TOP_N), float(t.RPN_NMS_THRESH), float(t.NMS_THRESH),
-            bool(t.get('NMS_ROTATED', False)), bool(t.get('CONV_BF16', False)),
+            bool(t.get('NMS_ROTATED', False)), bool(t.get('CONV_BF16', False)), bool(t.get('CONV_SPLIT_BF16', True)),
             str(t.get('MODE', 'nms')), int(t.get('RPN_TOP_N', 0)), str(cfg.POOLING_MODE), int(cfg.POOLING_SIZE),
             bool(cfg.ENABLE_CUSTOM_TAIL), uc, int(u.E_NUM_SAMPLE), int(u.A_NUM_CE_SAMPLE), ops.nms_suppress_at_equal(),
             ops._CONV_ALGO_MODE, ops._CONV_ALGO_FLAGS, bool(N.PROJECT_BEFORE_POOLING), bool(N.FUSE_PROJECTIONS),

@@ -156,8 +156,22 @@ def conv_bf16_wanted(x, w_krsc, stride, pad):
     return x.shape[-1] == c and conv_bf16_eligible(c, k, r, s, stride, pad)
 
 
-def _bf16_entry(holder, name, w_krsc):
-    """``w_krsc`` packed for ``ops.conv2d_nhwc_bf16``, cached on ``holder`` next to the fp32 filter it was made from and
+def conv_split_bf16_wanted(x, w_krsc, stride, pad):
+    """cfg.TEST.CONV_SPLIT_BF16, a TEST-mode forward, no gradient wanted, C % 32 == 0 and the library's rule
+    (``ops.conv_split_bf16_wanted``: the large GEMMs; no while a forced tile, ``set_conv_algo``, the staging mode or
+    ``frcnn_conv2d_split_bf16_enable(0)`` pins the fp32 kernels; an imported plan table does not) says yes."""
+    if not cfg.TEST.get('CONV_SPLIT_BF16', True) or _NET_MODE != 'TEST' or (torch.is_grad_enabled() and x.requires_grad):
+        return False
+    k, r, s, c = w_krsc.shape
+    if x.dim() != 4 or x.shape[-1] != c or not conv_bf16_eligible(c, k, r, s, stride, pad):
+        return False
+    n, h, w, _ = x.shape
+    return ops.conv_split_bf16_wanted(n, h, w, c, k, r, s, stride, pad)
+
+
+def _bf16_entry(holder, name, w_krsc, pack=None):
+    """``w_krsc`` packed for ``ops.conv2d_nhwc_bf16`` (``pack``: another packer - ``ops.conv2d_pack_bf16x3`` for the split
+    form, under a name of its own), cached on ``holder`` next to the fp32 filter it was made from and
     re-packed IN PLACE when that filter changed (also the entry's refresh hook, after the filter's own).  A cache miss
     inside a stream capture would launch the packing into the graph and pin a graph-pool tensor on the module: it raises
     instead (run one eager frame first)."""
@@ -167,18 +181,23 @@ def _bf16_entry(holder, name, w_krsc):
         return cache[1][0]
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("bf16 filter of a %s layer is not prepared: run an eager frame before capturing" % (tuple(w_krsc.shape),))
-    return stable_store(holder, name, key, (ops.conv2d_pack_bf16(w_krsc),), refresh=lambda: _bf16_entry(holder, name, w_krsc))[0]
+    packed = (pack or ops.conv2d_pack_bf16)(w_krsc)
+    return stable_store(holder, name, key, (packed,), refresh=lambda: _bf16_entry(holder, name, w_krsc, pack))[0]
 
 
 def conv_forward(x, w_krsc, scale, shift, residual, holder, stride=1, pad=0, relu=False, winograd_of=None,
                  cache_name='_frcnn_bf16'):
     """The one forward convolution of the inference call sites.  With cfg.TEST.CONV_BF16 in a TEST-mode forward an eligible
     layer (``conv_bf16_eligible``) runs ``ops.conv2d_nhwc_bf16`` on its packed filter, cached on ``holder`` under
-    ``cache_name``; every other call is ``ops.conv2d_nhwc`` exactly as without the switch (``winograd_of``: the module whose
+    ``cache_name``; after it, with cfg.TEST.CONV_SPLIT_BF16 (default on), a layer the library's rule selects runs the
+    fp32-accurate ``ops.conv2d_nhwc_bf16x3`` (filter cached under ``cache_name + 'x3'``); every other call is ``ops.conv2d_nhwc`` exactly as without the switch (``winograd_of``: the module whose
     pre-transformed Winograd filter a residual-free call may read)."""
     if conv_bf16_wanted(x, w_krsc, stride, pad):
         return ops.conv2d_nhwc_bf16(x, _bf16_entry(holder, cache_name, w_krsc), scale, shift, residual, stride=stride, pad=pad,
                                     relu=relu)
+    if conv_split_bf16_wanted(x, w_krsc, stride, pad):
+        return ops.conv2d_nhwc_bf16x3(x, _bf16_entry(holder, cache_name + 'x3', w_krsc, ops.conv2d_pack_bf16x3), scale, shift,
+                                      residual, stride=stride, pad=pad, relu=relu)
     u = None
     if winograd_of is not None and residual is None:
         n, h, wd, c = x.shape

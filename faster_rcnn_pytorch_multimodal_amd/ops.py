@@ -229,46 +229,84 @@ def set_conv_bf16_tile(mode):
 def conv2d_nhwc_bf16(x, w_bf16, scale=None, shift=None, residual=None, stride=1, pad=0, relu=False, out=None):
     """y = act(conv(bf16(x), w_bf16) * scale + shift + residual) with fp32 accumulation  —  frcnn_conv2d_fwd_bf16.  x, scale,
     shift, residual and y are fp32 as for ``conv2d_nhwc``; ``w_bf16`` comes from ``conv2d_pack_bf16``.  Needs C % 32 == 0."""
+    return _conv2d_nhwc_packed("conv2d_nhwc_bf16", "frcnn_conv2d_fwd_bf16", 1, x, w_bf16, scale, shift, residual, stride, pad, relu, out)
+
+
+def conv2d_pack_bf16x3(w_krsc):
+    """(K,R,S,C) fp32 filter -> (3,K,R,S,C) bf16 words (int16 tensor): hi = bf16(w), mid = bf16(w - hi), lo = bf16(w - hi - mid),
+    round to nearest even, hi + mid + lo == w.  The filter operand of ``conv2d_nhwc_bf16x3`` (frcnn_conv2d_pack_bf16x3);
+    constant while the weights are."""
+    _dev_f32(w_krsc, "w")
+    if w_krsc.dim() != 4:
+        raise _hip.HipError("conv2d_pack_bf16x3: need a (k,r,s,c) filter, got shape %s" % (tuple(w_krsc.shape),))
+    lib = _hip.load()
+    k, r, s, c = w_krsc.shape
+    out = torch.empty((3, k, r, s, c), dtype=torch.int16, device=w_krsc.device)
+    _hip.check(lib.frcnn_conv2d_pack_bf16x3(_ptr(w_krsc), _ptr(out), k, r, s, c, _stream()), "frcnn_conv2d_pack_bf16x3")
+    return out
+
+
+def conv2d_nhwc_bf16x3(x, w_bf16x3, scale=None, shift=None, residual=None, stride=1, pad=0, relu=False, out=None):
+    """y = act(conv(x, w) * scale + shift + residual) to fp32 accuracy on the bf16 matrix pipe  —  frcnn_conv2d_fwd_bf16x3:
+    every product as six bf16 products of the operands' hi / mid / lo planes, fp32 accumulation.  ``w_bf16x3`` comes from
+    ``conv2d_pack_bf16x3``.  Needs C % 32 == 0; for finite operands below about 2^120 (an infinite operand gives NaN)."""
+    return _conv2d_nhwc_packed("conv2d_nhwc_bf16x3", "frcnn_conv2d_fwd_bf16x3", 3, x, w_bf16x3, scale, shift, residual, stride, pad, relu, out)
+
+
+def conv_split_bf16_wanted(n, h, w, c, k, r, s, stride, pad):
+    """Does the library's rule give this convolution to the split-bf16 kernel (frcnn_conv2d_split_bf16_wanted)?  False
+    while a hook pins the fp32 kernels - a forced tile, ``set_conv_algo`` (mode or flags) or the staging mode away from
+    their defaults - and after ``frcnn_conv2d_split_bf16_enable(0)``.  An imported plan table does not pin it."""
+    args = [int(v) for v in (n, h, w, c, k, r, s, stride, pad)]
+    if min(args[:8]) < 1 or args[8] < 0:
+        raise _hip.HipError("conv_split_bf16_wanted: bad geometry n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d" % tuple(args))
+    return bool(_hip.load().frcnn_conv2d_split_bf16_wanted(*args))
+
+
+def _conv2d_nhwc_packed(what, entry, planes, x, w_bf16, scale, shift, residual, stride, pad, relu, out):
+    """The bf16-operand wrappers' common body: ``w_bf16`` is (k,r,s,c) for one plane, (3,k,r,s,c) for the split form."""
     _dev_f32(x, "x")
     if not isinstance(w_bf16, torch.Tensor) or not w_bf16.is_cuda:
         raise _hip.HipError("w_bf16 must be a tensor on the MI355X (got %s); this package has no CPU path"
                             % (getattr(w_bf16, "device", type(w_bf16)),))
-    if w_bf16.dtype != torch.int16 or not w_bf16.is_contiguous() or w_bf16.dim() != 4:
-        raise _hip.HipError("w_bf16 must be a contiguous (k,r,s,c) int16 tensor of bf16 words (conv2d_pack_bf16), got %s %s"
-                            % (w_bf16.dtype, tuple(w_bf16.shape)))
+    layout, packer = ("(k,r,s,c)", "conv2d_pack_bf16") if planes == 1 else ("(3,k,r,s,c)", "conv2d_pack_bf16x3")
+    if (w_bf16.dtype != torch.int16 or not w_bf16.is_contiguous() or w_bf16.dim() != (4 if planes == 1 else 5)
+            or (planes != 1 and w_bf16.shape[0] != planes)):
+        raise _hip.HipError("w_bf16 must be a contiguous %s int16 tensor of bf16 words (%s), got %s %s"
+                            % (layout, packer, w_bf16.dtype, tuple(w_bf16.shape)))
     if x.dim() != 4:
-        raise _hip.HipError("conv2d_nhwc_bf16: x must be (n,h,w,c), got shape %s" % (tuple(x.shape),))
+        raise _hip.HipError("%s: x must be (n,h,w,c), got shape %s" % (what, tuple(x.shape)))
     n, h, w, c = x.shape
-    k, r, s, c2 = w_bf16.shape
+    k, r, s, c2 = w_bf16.shape[-4:]
     if c2 != c:
-        raise _hip.HipError("conv2d_nhwc_bf16: input has %d channels, filter expects %d" % (c, c2))
+        raise _hip.HipError("%s: input has %d channels, filter expects %d" % (what, c, c2))
     if c % 32 != 0:
-        raise _hip.HipError("conv2d_nhwc_bf16: needs c %% 32 == 0, got c = %d" % c)
+        raise _hip.HipError("%s: needs c %% 32 == 0, got c = %d" % (what, c))
     stride, pad = int(stride), int(pad)
     if stride < 1 or pad < 0 or h + 2 * pad < r or w + 2 * pad < s:
-        raise _hip.HipError("conv2d_nhwc_bf16: bad geometry h=%d w=%d r=%d s=%d stride=%d pad=%d" % (h, w, r, s, stride, pad))
+        raise _hip.HipError("%s: bad geometry h=%d w=%d r=%d s=%d stride=%d pad=%d" % (what, h, w, r, s, stride, pad))
     for nm, t in (("scale", scale), ("shift", shift)):
         if t is not None:
             _dev_f32(t, nm)
             if t.numel() != k:
-                raise _hip.HipError("conv2d_nhwc_bf16: %s has %d elements, expected %d" % (nm, t.numel(), k))
+                raise _hip.HipError("%s: %s has %d elements, expected %d" % (what, nm, t.numel(), k))
     ho, wo = conv_out_hw(h, w, r, s, stride, pad)
     if out is None:
         out = torch.empty((n, ho, wo, k), dtype=torch.float32, device=x.device)
     else:
         _dev_f32(out, "out")
         if tuple(out.shape) != (n, ho, wo, k):
-            raise _hip.HipError("conv2d_nhwc_bf16: out has shape %s, expected %s" % (tuple(out.shape), (n, ho, wo, k)))
+            raise _hip.HipError("%s: out has shape %s, expected %s" % (what, tuple(out.shape), (n, ho, wo, k)))
     if residual is not None:
         _dev_f32(residual, "residual")
         if tuple(residual.shape) != (n, ho, wo, k):
-            raise _hip.HipError("conv2d_nhwc_bf16: residual shape %s != output shape %s" % (tuple(residual.shape), (n, ho, wo, k)))
-    _hip.check(_hip.load().frcnn_conv2d_fwd_bf16(_ptr(x), _ptr(w_bf16), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(out), n, h,
-                                                 w, c, k, r, s, stride, pad, int(bool(relu)), _stream()), "frcnn_conv2d_fwd_bf16")
+            raise _hip.HipError("%s: residual shape %s != output shape %s" % (what, tuple(residual.shape), (n, ho, wo, k)))
+    _hip.check(getattr(_hip.load(), entry)(_ptr(x), _ptr(w_bf16), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(out), n, h,
+                                           w, c, k, r, s, stride, pad, int(bool(relu)), _stream()), entry)
     if PROFILE is not None:
         PROFILE.append({"n": n, "h": h, "w": w, "c": c, "k": k, "r": r, "s": s, "stride": stride, "pad": pad,
                         "residual": residual is not None, "relu": bool(relu), "flops": 2.0 * n * ho * wo * k * r * s * c,
-                        "bf16": True})
+                        ("bf16" if planes == 1 else "split_bf16"): True})
     if FLOPS is not None:
         _log_flops('fwd', 2.0 * n * ho * wo * k * r * s * c)
     return out

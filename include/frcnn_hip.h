@@ -227,6 +227,34 @@ int frcnn_conv2d_fwd_bf16(const float* x, const void* w_bf16, const float* scale
                           int pad, int relu, void* stream);
 int frcnn_conv2d_bf16_set_tile(int mode);
 
+/* fp32-accurate form of frcnn_conv2d_fwd on the bf16 matrix pipe (same signature and semantics as frcnn_conv2d_fwd_bf16).
+ * Every fp32 operand is the exact sum of three bf16 values hi + mid + lo (hi = bf16(v), mid = bf16(v - hi),
+ * lo = bf16(v - hi - mid), round to nearest even); each product x * w is formed as six bf16 products accumulated in fp32,
+ * per k = 16 group in the order
+ *     x_lo*w_hi, x_hi*w_lo, x_mid*w_mid, x_mid*w_hi, x_hi*w_mid, x_hi*w_hi
+ * with the groups in ascending k (taps r, s, then channels, as frcnn_conv2d_fwd_bf16): the first five into one fp32
+ * accumulator per output, x_hi*w_hi into a second one, the two added once after the last group (small products added
+ * straight into the large sum lose low bits inside the MFMA).  The three terms left out are at most 2^-26 of the
+ * product.  Both tiles (frcnn_conv2d_bf16_set_tile applies) give bit-identical results.
+ * OPERAND RANGE: finite operands of magnitude below about 2^120.  An infinite operand gives NaN where fp32 gives infinity
+ * (its remainder is inf - inf); the remainders of operands within 2^16 of the smallest normal may flush to zero, so those
+ * operands are carried with fewer than 24 bits.
+ * frcnn_conv2d_pack_bf16x3 writes the filter as three (k,r,s,c) planes of 16-bit words, hi then mid then lo
+ * (frcnn_conv2d_pack_bf16x3_bytes bytes), once per weight version; x is split inside the kernel, once per tile element.
+ * frcnn_conv2d_split_bf16_wanted: 1 where this kernel is to replace the fp32 plan - a rule in the GEMM's dimensions
+ * (M = n*ho*wo, N = k, Ktot = r*s*c): c % 32 == 0, ceil(M/128) * ceil(N/128) >= 256, N >= 512 and Ktot >= 512, and no
+ * Winograd form (3x3, stride 1, pad 1 stays with fp32 F(2x2, 3x3), which measured faster).  It answers
+ * 0 while frcnn_conv2d_set_tile forces a tile, frcnn_conv2d_set_algo / _set_staging are not at their defaults, or after
+ * frcnn_conv2d_split_bf16_enable(0)
+ * (test hook, part of frcnn_settings_signature). */
+size_t frcnn_conv2d_pack_bf16x3_bytes(int k, int r, int s, int c);
+int frcnn_conv2d_pack_bf16x3(const float* w_krsc, void* w_bf16x3, int k, int r, int s, int c, void* stream);
+int frcnn_conv2d_fwd_bf16x3(const float* x, const void* w_bf16x3, const float* scale, const float* shift,
+                            const float* residual, float* y, int n, int h, int w, int c, int k, int r, int s, int stride,
+                            int pad, int relu, void* stream);
+int frcnn_conv2d_split_bf16_wanted(int n, int h, int w, int c, int k, int r, int s, int stride, int pad);
+int frcnn_conv2d_split_bf16_enable(int on);
+
 /* nn.MaxPool2d(kernel_size=3, stride=2, padding=1)  (lib/nets/resnet.py:156), NHWC. */
 int frcnn_maxpool3x3s2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
 /* Its backward (trainable stem, cfg.RESNET.FIXED_BLOCKS == -1): dx (n,h,w,c) receives dy of every window whose first
