@@ -430,6 +430,8 @@ extern "C" int frcnn_upsample_bilinear_add_fwd(const float* x, const float* late
                                                int out_h, int out_w, int c, void* stream_) {
   FRCNN_REQUIRE(x && lateral && out && n > 0 && h > 0 && w > 0 && out_h > 0 && out_w > 0 && c > 0 && c % 4 == 0,
                 "upsample_bilinear_add_fwd: bad arguments (c%%4==0)");
+  // the FPN's top-down path only enlarges (lib/nets/fpn.py:42-45: a coarser level onto the finer lateral)
+  FRCNN_REQUIRE(out_h >= h && out_w >= w, "upsample_bilinear_add_fwd: output %dx%d smaller than the input %dx%d", out_h, out_w, h, w);
   const size_t total = (size_t)n * out_h * out_w * (c / 4);
   hipLaunchKernelGGL(upsample_add_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream_), x,
                      lateral, n, h, w, out_h, out_w, c / 4, out);
@@ -440,6 +442,7 @@ extern "C" int frcnn_upsample_bilinear_bwd(const float* dout, float* dx, int n, 
                                            int c, void* stream_) {
   FRCNN_REQUIRE(dout && dx && n > 0 && h > 0 && w > 0 && out_h > 0 && out_w > 0 && c > 0 && c % 4 == 0,
                 "upsample_bilinear_bwd: bad arguments (c%%4==0)");
+  FRCNN_REQUIRE(out_h >= h && out_w >= w, "upsample_bilinear_bwd: output %dx%d smaller than the input %dx%d", out_h, out_w, h, w);
   const size_t total = (size_t)n * h * w * (c / 4);
   hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream_), dout, n,
                      h, w, out_h, out_w, c / 4, dx);

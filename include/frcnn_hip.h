@@ -661,7 +661,8 @@ int frcnn_spatial_mean_bwd(const float* dout, float* dx, int rows, int pooled, i
 
 /* fpn._upsample_add (lib/nets/fpn.py:42-45): out (n,out_h,out_w,c) = F.interpolate(x (n,h,w,c), size=(out_h,out_w),
  * mode='bilinear', align_corners=False) + lateral.  Backward: dx = interpolate^T(dout) (deterministic gather);
- * the gradient of `lateral` is dout itself. */
+ * the gradient of `lateral` is dout itself.  The top-down path only enlarges (c5 -> c4 -> c3 -> c2 maps): out_h < h or
+ * out_w < w is rejected by both entry points. */
 int frcnn_upsample_bilinear_add_fwd(const float* x, const float* lateral, float* out, int n, int h, int w,
                                     int out_h, int out_w, int c, void* stream);
 int frcnn_upsample_bilinear_bwd(const float* dout, float* dx, int n, int h, int w, int out_h, int out_w, int c,

@@ -1,0 +1,819 @@
+"""The gather, resampling and compaction kernels between the big ones, at their edges: gather_rows / make_rois
+(csrc/boxes.hip), upsample_bilinear_add_fwd / _bwd (csrc/train_ops.hip), maxpool3x3s2_fwd / _bwd and pad_channels
+(csrc/conv_igemm.hip), prep_image (csrc/prep.hip), labelled_pixels / gather_patches / scatter_add_patches
+(csrc/targets.hip).  Each is called directly through ops.py, or through the C ABI where ops.py hides an argument
+(roi_scores == NULL, pad_channels with c == c_pad), and compared with a reference that does not come from the code under
+test: plain indexing for the copies, F.interpolate / F.max_pool2d and their autograd, O.prep_im_for_blob, float64 sums.
+
+Case builders return (inputs, reference, bars).  The unmarked ``test_cpu_restatement_*`` tests restate each kernel's
+arithmetic in float32 numpy, in the kernel's own order, and must meet the same bars with 4x headroom (bit for bit where
+the GPU test asks for that).
+
+Which case reaches which regime (case ids as pytest prints them):
+  gather_rows width                w1 (1-D rows) w4 w5 w7
+  device count                     cnt0, cntmid, cntmax, cntover (above max_count: clamped), cntnull (count == NULL)
+  order                            perm (a permutation), rep (repeats); dead rows hold valid indices and must come out 0
+  stride loop, second trip         gather big-w7: max_count * width = 75000 * 7 > 2048 * 256
+  make_rois                        cnt0 / cntmid / cntmax / cntover x perm / rep, m = 700 (three blocks, ragged last);
+                                   roi_scores == NULL through the C ABI; dead boxes AND dead scores exactly 0
+  upsample shapes                  1x1-7x5 (one source pixel), 1x9-4x9 (one row, identity in x), 3x2-10x9 (ratios 3.3 / 4.5),
+                                   2x3-9x11 (4.5 / 3.7), 5x7-5x7 (identity: bit for bit), 4x4-19x17 (4.75 / 4.25),
+                                   44x50-45x53 with N = 1000 (1000 x 45 x 53 and 1000 x 44 x 50 items > 8192 * 256: second trip, both ways)
+  upsample, output < input         rejected by both entry points: the FPN's top-down path only enlarges (nets/fpn.py)
+  maxpool maps                     1x1 1x9 9x1 2x2 7x8; fwd 1x726x726x64 (363 x 363 x 16 items > 8192 * 256); bwd 1x1450x1450x4
+  maxpool inputs                   randn, neg (all negative: a zero pad would win), inf (-inf, whole windows of it)
+  maxpool backward                 ties (integers in -3..3) against autograd; conservation sum(dx) == sum(dy) per channel
+  pad_channels                     1-4, 3-4, 3-8, 4-4 (a copy, through the C ABI), big (525000 x 4 > 8192 * 256)
+  prep_image scales                1.0 (bit-exact (px - mean) / std), 0.5 on 37 x 53 (18.5 -> 18, 26.5 -> 26: half-even), 0.3, 1.3, 2.0, 3.7
+  prep_image images                1x1, 1x40, 40x1 (where the output is not empty), 37x53, 1100x1000 at 1.0 (> 4096 * 256 pixels)
+  prep_image channels              c_out 3 and 4 in every case (fourth channel exactly 0), all six orders on 37x53-s1.3
+  prep_image, empty output         1x40 at 0.5 (round-half-even(0.5) = 0): rejected
+  labelled_pixels hw / A           hw1 hw1023 hw1024 hw1025 hw2500 x A1 A9 (passes of 1024 pixels: one, one short, exact, one over, 3)
+  labelled sets                    none, all-capover, all-capunder, last, edges (pixels k * 1024 +- 1)
+  gather / scatter patches         1x1 pad 0 and 3x3 pad 1 on the four corners and an interior pixel of a 5 x 7 map, cap > count;
+                                   scatter with overlapping neighbours against a float64 scatter, and the adjoint identity
+
+Bars.  Bit for bit: gather_rows, make_rois, pad_channels, maxpool forward (F.max_pool2d), gather_patches, labelled_pixels,
+prep_image at scale 1.0, the upsample at the identity shape.  Upsample: 1e-5 forward / 2e-5 backward against F.interpolate
+and its autograd in float32 (tests/test_gpu_parity.py), times max(1, max |reference|).  prep_image: 2e-5 (the existing test)
+times max(1, max |reference|).  Maxpool backward: 1e-6 against autograd (the existing test).  The sums (adjoint identities,
+conservation, scatter) have bars derived from float32 rounding next to the case: (number of roundings) x U / 2 x the sum of
+the magnitudes that enter, which the restatement must meet with 4x headroom.
+"""
+import functools
+import itertools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import frcnn_oracle as O
+
+DEV = "cuda:0"
+U = 2.0 ** -23
+HEADROOM = 4.0
+f32 = np.float32
+GATHER_CAP = 2048 * 256              # gather_rows: min(ceil(total / 256), 2048) blocks of 256, then stride
+GRID_CAP = 8192 * 256                # upsample, maxpool, pad_channels
+PREP_CAP = 4096 * 256                # prep_image
+
+
+def _ops():
+    from faster_rcnn_pytorch_multimodal_amd import ops
+    return ops
+
+
+def _hip():
+    from faster_rcnn_pytorch_multimodal_amd import _hip
+    return _hip
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _assert_bits(section, case, name, got, want):
+    got = np.ascontiguousarray(_np(got) if torch.is_tensor(got) else got)
+    want = np.ascontiguousarray(_np(want) if torch.is_tensor(want) else want)
+    assert got.shape == want.shape and got.dtype == want.dtype, (section, case, name, got.shape, want.shape, got.dtype, want.dtype)
+    if got.dtype == np.float32:
+        gn, wn = np.isnan(got), np.isnan(want)
+        assert np.array_equal(gn, wn), (section, case, name, "NaN positions differ")
+        bad = np.flatnonzero((got.view(np.int32) != want.view(np.int32)).reshape(-1) & ~gn.reshape(-1))
+    else:
+        bad = np.flatnonzero((got != want).reshape(-1))
+    print("CHK|%s|bits|%s|%s|differing=%d of %d" % (section, case, name, bad.size, got.size))
+    if bad.size:
+        i = int(bad[0])
+        raise AssertionError("%s %s %s: %d of %d elements differ; first at flat index %d: got %r, expected %r" % (
+            section, case, name, bad.size, got.size, i, got.reshape(-1)[i], want.reshape(-1)[i]))
+
+
+def _assert_close(section, case, name, got, ref, bar, side, headroom=1.0):
+    """max |got - ref| / bar <= 1 / headroom, everything finite; prints the figure before it asserts."""
+    got = np.asarray(_np(got) if torch.is_tensor(got) else got, dtype=np.float64).reshape(-1)
+    ref = np.asarray(_np(ref) if torch.is_tensor(ref) else ref, dtype=np.float64).reshape(-1)
+    assert got.shape == ref.shape, (section, case, name, got.shape, ref.shape)
+    assert np.isfinite(ref).all() and np.isfinite(got).all(), (section, case, name, "not finite")
+    bar_a = np.broadcast_to(np.asarray(bar, dtype=np.float64).reshape(-1), got.shape)
+    err = np.abs(got - ref)
+    ratio = float((err / bar_a).max()) if err.size else 0.0
+    print("CHK|%s|%s|%s|%s|err=%.3e|ratio=%.4f" % (section, side, case, name, float(err.max()) if err.size else 0.0, ratio))
+    assert ratio * headroom <= 1.0, "%s %s %s (%s): max err %.3e is %.3f of its bar, allowed %.3f" % (
+        section, case, name, side, float(err.max()), ratio, 1.0 / headroom)
+
+
+def _big(t):
+    return max(1.0, float(np.abs(_np(t) if torch.is_tensor(t) else t).max()))
+
+
+# ================================================================================================
+# 1. gather_rows / make_rois
+# ================================================================================================
+COUNTS = ["cnt0", "cntmid", "cntmax", "cntover", "cntnull"]
+GATHER_CASES = [(w, c, o, 61) for w in (1, 4, 5, 7) for c in COUNTS for o in ("perm", "rep")] + [(7, "cntmid", "rep", 75000)]
+
+
+def _gather_id(c):
+    return "%sw%d-%s-%s" % ("big-" if c[3] > 61 else "", c[0], c[1], c[2])
+
+
+def _count_value(kind, m):
+    return {"cnt0": 0, "cntmid": m // 2 + 1, "cntmax": m, "cntover": m + 9, "cntnull": None}[kind]
+
+
+def _order(kind, m, n_rows, g):
+    if kind == "perm":
+        return torch.randperm(n_rows, generator=g)[:m].contiguous()
+    return torch.randint(0, max(1, n_rows // 3), (m,), generator=g)
+
+
+@functools.lru_cache(maxsize=None)
+def gather_case(case):
+    width, ckind, okind, m = case
+    g = torch.Generator().manual_seed(100 + width + 7 * COUNTS.index(ckind) + m)
+    n_rows = m + 13
+    rows = torch.randn(n_rows, width, generator=g) + 3.0       # no zero among the live values: a dead row cannot pass for one
+    if width == 1:
+        rows = rows.view(-1)                                   # ops.gather_rows reads a 1-D tensor as width 1
+    order = _order(okind, m, n_rows, g)
+    cnt = _count_value(ckind, m)
+    live = m if cnt is None else min(cnt, m)
+    ref = rows.view(n_rows, width)[order].clone()
+    ref[live:] = 0
+    return dict(rows=rows, order=order, count=cnt), ref
+
+
+def gather32(rows, order, count, max_count, width):
+    """gather_rows_kernel element by element: i -> (r, c) = (i / width, i - r * width)."""
+    cnt = max_count if count is None else min(count, max_count)
+    i = np.arange(max_count * width)
+    r = i // width
+    c = i - r * width
+    flat = np.asarray(rows, dtype=f32).reshape(-1)
+    return np.where(r < cnt, flat[np.asarray(order)[r] * width + c], f32(0)).astype(f32).reshape(max_count, width)
+
+
+@pytest.mark.parametrize("case", GATHER_CASES, ids=_gather_id)
+def test_cpu_restatement_gather_rows(case):
+    inp, ref = gather_case(case)
+    got = gather32(_np(inp["rows"]), _np(inp["order"]), inp["count"], case[3], case[0])
+    _assert_bits("gather", _gather_id(case), "rows", got, ref)
+    live = case[3] if inp["count"] is None else min(inp["count"], case[3])
+    assert (got[live:] == 0).all() and (got[:live] != 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", GATHER_CASES, ids=_gather_id)
+def test_gather_rows(hip, case):
+    inp, ref = gather_case(case)
+    cnt = None if inp["count"] is None else torch.tensor([inp["count"]], dtype=torch.int32, device=DEV)
+    got = _ops().gather_rows(inp["rows"].to(DEV), inp["order"].to(DEV), cnt)
+    assert case[3] * case[0] > GATHER_CAP or case[3] == 61
+    _assert_bits("gather", _gather_id(case), "rows", got, ref)
+
+
+ROIS_CASES = [(c, o) for c in COUNTS[:4] for o in ("perm", "rep")]
+ROIS_M = 700
+
+
+@functools.lru_cache(maxsize=None)
+def rois_case(case):
+    ckind, okind = case
+    g = torch.Generator().manual_seed(200 + COUNTS.index(ckind))
+    n = ROIS_M + 50
+    boxes = torch.rand(n, 4, generator=g) * 500 + 1.0
+    scores = torch.rand(n, generator=g) + 0.5
+    keep = _order(okind, ROIS_M, n, g)
+    cnt = _count_value(ckind, ROIS_M)
+    live = min(cnt, ROIS_M)
+    rois = torch.cat((torch.zeros(ROIS_M, 1), boxes[keep]), 1)
+    sc = scores[keep].clone().view(-1, 1)
+    rois[live:] = 0
+    sc[live:] = 0
+    return dict(boxes=boxes, scores=scores, keep=keep, count=cnt), dict(rois=rois, scores=sc)
+
+
+@pytest.mark.parametrize("case", ROIS_CASES, ids=lambda c: "%s-%s" % c)
+def test_cpu_restatement_make_rois(case):
+    inp, ref = rois_case(case)
+    live = min(inp["count"], ROIS_M)
+    b, s, k = _np(inp["boxes"]), _np(inp["scores"]), _np(inp["keep"])
+    rois, sc = np.zeros((ROIS_M, 5), f32), np.zeros((ROIS_M, 1), f32)
+    for i in range(live):                                      # make_rois_kernel, one thread per row
+        rois[i, 1:] = b[k[i]]
+        sc[i, 0] = s[k[i]]
+    _assert_bits("make_rois", "%s-%s" % case, "rois", rois, ref["rois"])
+    _assert_bits("make_rois", "%s-%s" % case, "scores", sc, ref["scores"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ROIS_CASES, ids=lambda c: "%s-%s" % c)
+def test_make_rois(hip, case):
+    inp, ref = rois_case(case)
+    cid = "%s-%s" % case
+    boxes, scores, keep = inp["boxes"].to(DEV), inp["scores"].to(DEV), inp["keep"].to(DEV)
+    cnt = torch.tensor([inp["count"]], dtype=torch.int32, device=DEV)
+    rois, sc = _ops().make_rois(boxes, scores, keep, cnt)
+    _assert_bits("make_rois", cid, "rois", rois, ref["rois"])
+    _assert_bits("make_rois", cid, "scores", sc, ref["scores"])
+    # roi_scores == NULL: the same rois, nothing else written
+    bare = torch.full((ROIS_M, 5), -7.0, device=DEV)
+    rc = hip.frcnn_make_rois(boxes.data_ptr(), scores.data_ptr(), keep.data_ptr(), cnt.data_ptr(), ROIS_M, bare.data_ptr(), None,
+                             _stream())
+    assert rc == 0, hip.frcnn_last_error()
+    _assert_bits("make_rois", cid, "rois without roi_scores", bare, ref["rois"])
+
+
+# ================================================================================================
+# 2. upsample_bilinear_add_fwd / upsample_bilinear_bwd
+# ================================================================================================
+UP_SHAPES = [(1, 1, 7, 5), (1, 9, 4, 9), (3, 2, 10, 9), (2, 3, 9, 11), (5, 7, 5, 7), (4, 4, 19, 17)]
+UP_BIG = (44, 50, 45, 53)              # with UP_BIG_N images; small coordinates: the float32 source coordinate stays sharp
+UP_N, UP_C, UP_BIG_N = 3, 4, 1000
+
+
+def _up_id(s):
+    return "%dx%d-%dx%d" % s
+
+
+@functools.lru_cache(maxsize=None)
+def up_case(shape):
+    h, w, oh, ow = shape
+    g = torch.Generator().manual_seed(300 + h * 100 + w + oh)
+    n = UP_BIG_N if shape == UP_BIG else UP_N
+    x = torch.randn(n, h, w, UP_C, generator=g)
+    lat = torch.randn(n, oh, ow, UP_C, generator=g)
+    dout = torch.randn(n, oh, ow, UP_C, generator=g)
+    xr = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    up = F.interpolate(xr, size=(oh, ow), mode="bilinear", align_corners=False)
+    up.backward(dout.permute(0, 3, 1, 2).contiguous())
+    ref = dict(out=(up.detach() + lat.permute(0, 3, 1, 2)).permute(0, 2, 3, 1).contiguous(),
+               dx=xr.grad.permute(0, 2, 3, 1).contiguous())
+    bars = dict(out=1e-5 * _big(ref["out"]), dx=2e-5 * _big(ref["dx"]))
+    # adjoint identity <up(x), d> == <x, up_bwd(d)> in float64 from float32 results.  Forward: seven roundings in the blend
+    # (weights <= 1) and one in the lateral add, each U / 2 of (|up| + |lateral|) at most, and up = out - lateral takes the
+    # add's rounding back out only to that accuracy.  Backward: a source pixel sums T products of three factors, T <= the taps of its window
+    # (all oh * ow destination pixels at most): (T + 2) U / 2 of sum |weight x d| = the adjoint applied to |d|.
+    ar = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    F.interpolate(ar, size=(oh, ow), mode="bilinear", align_corners=False).backward(dout.permute(0, 3, 1, 2).abs().contiguous())
+    absadj = ar.grad.permute(0, 2, 3, 1).double()
+    taps = min(oh * ow, (2 * (oh + h - 1) // h + 3) * (2 * (ow + w - 1) // w + 3))
+    up_abs = (ref["out"] - lat).double().abs()
+    bars["adjoint"] = float(8 * (U / 2) * (dout.double().abs() * (up_abs + lat.double().abs())).sum() +
+                            (taps + 2) * (U / 2) * (x.double().abs() * absadj).sum())
+    return dict(x=x, lat=lat, dout=dout), ref, bars
+
+
+def _tap32(n_out, n_in):
+    """bilinear_tap of csrc/train_ops.hip for every destination index."""
+    ratio = f32(n_in) / f32(n_out)
+    src = (np.arange(n_out, dtype=f32) + f32(0.5)) * ratio - f32(0.5)
+    src = np.where(src < 0, f32(0), src).astype(f32)
+    i0 = src.astype(np.int64)
+    i1 = i0 + (i0 < n_in - 1)
+    l1 = src - i0.astype(f32)
+    return i0, i1, f32(1) - l1, l1
+
+
+def up_fwd32(x, lat):
+    _, h, w, _ = x.shape
+    _, oh, ow, _ = lat.shape
+    y0, y1, b0, b1 = _tap32(oh, h)
+    x0, x1, a0, a1 = _tap32(ow, w)
+    a0, a1, b0, b1 = a0[None, None, :, None], a1[None, None, :, None], b0[None, :, None, None], b1[None, :, None, None]
+    v = lambda yi, xi: x[:, yi][:, :, xi]
+    return (b0 * (a0 * v(y0, x0) + a1 * v(y0, x1)) + b1 * (a0 * v(y1, x0) + a1 * v(y1, x1))) + lat
+
+
+def up_bwd32(dout, h, w):
+    """upsample_bwd_kernel: every source pixel gathers in (Y, X) order from the destination pixels whose taps touch it."""
+    n, oh, ow, c = dout.shape
+    y0, y1, b0, b1 = _tap32(oh, h)
+    x0, x1, a0, a1 = _tap32(ow, w)
+    dx = np.zeros((n, h, w, c), f32)
+    for ys in range(h):
+        wy = np.where(y0 == ys, b0, f32(0)) + np.where(y1 == ys, b1, f32(0))
+        for xs in range(w):
+            wx = np.where(x0 == xs, a0, f32(0)) + np.where(x1 == xs, a1, f32(0))
+            acc = np.zeros((n, c), f32)
+            for yy in np.flatnonzero(wy != 0):
+                for xx in np.flatnonzero(wx != 0):
+                    acc = acc + (wy[yy] * wx[xx]) * dout[:, yy, xx, :]
+            dx[:, ys, xs, :] = acc
+    return dx
+
+
+def _adjoint_gap(out, lat, dout, x, dx):
+    d64 = lambda a: np.asarray(_np(a) if torch.is_tensor(a) else a, dtype=np.float64)
+    lhs = float(((d64(out) - d64(lat)) * d64(dout)).sum())
+    rhs = float((d64(x) * d64(dx)).sum())
+    return lhs, rhs
+
+
+@pytest.mark.parametrize("shape", UP_SHAPES, ids=_up_id)
+def test_cpu_restatement_upsample(shape):
+    inp, ref, bars = up_case(shape)
+    x, lat, dout = _np(inp["x"]), _np(inp["lat"]), _np(inp["dout"])
+    out, dx = up_fwd32(x, lat), up_bwd32(dout, shape[0], shape[1])
+    _assert_close("upsample", _up_id(shape), "out", out, ref["out"], bars["out"], "cpu", HEADROOM)
+    _assert_close("upsample", _up_id(shape), "dx", dx, ref["dx"], bars["dx"], "cpu", HEADROOM)
+    lhs, rhs = _adjoint_gap(out, lat, dout, x, dx)
+    _assert_close("upsample", _up_id(shape), "adjoint", lhs, rhs, bars["adjoint"], "cpu", HEADROOM)
+    if shape[:2] == shape[2:]:
+        _assert_bits("upsample", _up_id(shape), "out == x + lateral", out, x + lat)
+        _assert_bits("upsample", _up_id(shape), "dx == dout", dx, dout)
+
+
+def test_cpu_restatement_upsample_big_forward():
+    """The second-trip shape: the forward restatement only (the backward restatement is a Python loop over source pixels)."""
+    inp, ref, bars = up_case(UP_BIG)
+    _assert_close("upsample", _up_id(UP_BIG), "out", up_fwd32(_np(inp["x"]), _np(inp["lat"])), ref["out"], bars["out"], "cpu", HEADROOM)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", UP_SHAPES + [UP_BIG], ids=_up_id)
+def test_upsample_bilinear_edges(hip, shape):
+    ops, cid = _ops(), _up_id(shape)
+    h, w, oh, ow = shape
+    inp, ref, bars = up_case(shape)
+    x, lat, dout = inp["x"].to(DEV), inp["lat"].to(DEV), inp["dout"].to(DEV)
+    if shape == UP_BIG:
+        assert UP_BIG_N * oh * ow * (UP_C // 4) > GRID_CAP and UP_BIG_N * h * w * (UP_C // 4) > GRID_CAP
+    out = ops.upsample_bilinear_add(x, lat)
+    dx = ops.upsample_bilinear_bwd(dout, (h, w))
+    _assert_close("upsample", cid, "out", out, ref["out"], bars["out"], "gpu")
+    _assert_close("upsample", cid, "dx", dx, ref["dx"], bars["dx"], "gpu")
+    lhs, rhs = _adjoint_gap(out, lat, dout, x, dx)
+    _assert_close("upsample", cid, "adjoint", lhs, rhs, bars["adjoint"], "gpu")
+    if (h, w) == (oh, ow):
+        _assert_bits("upsample", cid, "out == x + lateral", out, inp["x"] + inp["lat"])
+        _assert_bits("upsample", cid, "dx == dout", dx, inp["dout"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(5, 7, 4, 7), (5, 7, 5, 6), (4, 4, 2, 2)], ids=_up_id)
+def test_upsample_rejects_an_output_smaller_than_the_input(hip, shape):
+    """lib/nets/fpn.py:42-45 interpolates a coarser level to the size of the finer lateral map (p5 -> c4, p4 -> c3, p3 -> c2;
+    the backbone halves with ceil, so a coarser map is never larger): nothing asks for a reduction, and both entry points
+    refuse one with a message instead of resampling without an anti-alias filter."""
+    ops = _ops()
+    h, w, oh, ow = shape
+    x, lat = torch.zeros(1, h, w, 4, device=DEV), torch.zeros(1, oh, ow, 4, device=DEV)
+    with pytest.raises(_hip().HipError, match="smaller than the input"):
+        ops.upsample_bilinear_add(x, lat)
+    with pytest.raises(_hip().HipError, match="smaller than the input"):
+        ops.upsample_bilinear_bwd(lat, (h, w))
+
+
+# ================================================================================================
+# 3. maxpool3x3s2_fwd / _bwd, pad_channels
+# ================================================================================================
+POOL_MAPS = [(1, 1), (1, 9), (9, 1), (2, 2), (7, 8)]
+POOL_KINDS = ["randn", "neg", "inf"]
+POOL_FWD_BIG = (1, 726, 726, 64)
+POOL_BWD_BIG = (1, 1450, 1450, 4)
+
+
+def _pool_input(shape, kind, g):
+    x = torch.randn(shape, generator=g)
+    if kind == "neg":
+        x = -(x.abs() + 0.5)
+    elif kind == "inf":
+        x[torch.rand(shape, generator=g) < 0.4] = float("-inf")
+        x[:, : (shape[1] + 1) // 2, : (shape[2] + 1) // 2] = float("-inf")       # whole windows of -inf as well
+    return x
+
+
+def pool_fwd32(x):
+    """maxpool3x3s2_nhwc: running fmaxf from -inf over the window positions that lie inside the map."""
+    n, h, w, c = x.shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    xp = np.full((n, 2 * ho + 1, 2 * wo + 1, c), -np.inf, f32)
+    xp[:, 1:h + 1, 1:w + 1] = x
+    m = np.full((n, ho, wo, c), -np.inf, f32)
+    for dy in range(3):
+        for dx in range(3):
+            m = np.maximum(m, xp[:, dy:dy + 2 * ho:2, dx:dx + 2 * wo:2])
+    return m
+
+
+def pool_bwd32(x, dy):
+    """maxpool3x3s2_bwd_nhwc: each window hands its dy to its first maximum in row-major order; a pixel adds the windows it
+    wins in (ho, wo) order."""
+    n, h, w, c = x.shape
+    ho, wo = dy.shape[1], dy.shape[2]
+    xp = np.full((n, 2 * ho + 1, 2 * wo + 1, c), -np.inf, f32)
+    xp[:, 1:h + 1, 1:w + 1] = x
+    win = np.stack([xp[:, a:a + 2 * ho:2, b:b + 2 * wo:2] for a in range(3) for b in range(3)], -1)      # (n, ho, wo, c, 9)
+    first = win.argmax(-1)                                     # numpy returns the first maximum
+    hi = 2 * np.arange(ho)[None, :, None, None] - 1 + first // 3
+    wi = 2 * np.arange(wo)[None, None, :, None] - 1 + first % 3
+    dx = np.zeros((n, h, w, c), f32)
+    ni = np.broadcast_to(np.arange(n)[:, None, None, None], first.shape)
+    ci = np.broadcast_to(np.arange(c)[None, None, None, :], first.shape)
+    for a in range(ho):                                        # window order = the kernel's accumulation order
+        for b in range(wo):
+            np.add.at(dx, (ni[:, a, b], hi[:, a, b], wi[:, a, b], ci[:, a, b]), dy[:, a, b])
+    return dx
+
+
+@functools.lru_cache(maxsize=None)
+def pool_fwd_case(shape, kind):
+    g = torch.Generator().manual_seed(400 + sum(shape) + POOL_KINDS.index(kind))
+    x = _pool_input(shape, kind, g)
+    ref = F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).contiguous()
+    return x, ref
+
+
+@functools.lru_cache(maxsize=None)
+def pool_bwd_case(shape):
+    g = torch.Generator().manual_seed(500 + sum(shape))
+    x = torch.randint(-3, 4, shape, generator=g).float()       # many ties inside every window
+    xr = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    y = F.max_pool2d(xr, 3, 2, 1)
+    dy = torch.randn(y.shape, generator=g)
+    y.backward(dy)
+    dy = dy.permute(0, 2, 3, 1).contiguous()
+    ref = xr.grad.permute(0, 2, 3, 1).contiguous()
+    # conservation: every window routes its dy to exactly one pixel, so a channel's dx sums to its dy.  A pixel adds at most
+    # four dy in float32: three roundings of U / 2 of the magnitudes added
+    bars = dict(dx=1e-6 * _big(ref), conservation=3 * (U / 2) * dy.double().abs().sum((0, 1, 2)).numpy() + 1e-30)
+    return dict(x=x, dy=dy), ref, bars
+
+
+def _pool_id(p):
+    return "%dx%d-%s" % (p[0][0], p[0][1], p[1])
+
+
+POOL_FWD_CASES = [(m, k) for m in POOL_MAPS for k in POOL_KINDS]
+
+
+@pytest.mark.parametrize("case", POOL_FWD_CASES, ids=_pool_id)
+def test_cpu_restatement_maxpool_fwd(case):
+    (h, w), kind = case
+    x, ref = pool_fwd_case((2, h, w, 8), kind)
+    _assert_bits("maxpool", _pool_id(case), "y", pool_fwd32(_np(x)), ref)
+    if kind == "neg":
+        assert float(ref.max()) < 0
+    if kind == "inf":
+        assert bool(torch.isinf(ref).any())
+
+
+@pytest.mark.parametrize("hw", POOL_MAPS, ids=lambda m: "%dx%d" % m)
+def test_cpu_restatement_maxpool_bwd(hw):
+    inp, ref, bars = pool_bwd_case((2, hw[0], hw[1], 8))
+    dx = pool_bwd32(_np(inp["x"]), _np(inp["dy"]))
+    _assert_close("maxpool_bwd", "%dx%d" % hw, "dx", dx, ref, bars["dx"], "cpu", HEADROOM)
+    _assert_close("maxpool_bwd", "%dx%d" % hw, "conservation", dx.astype(np.float64).sum((0, 1, 2)),
+                  inp["dy"].double().sum((0, 1, 2)), bars["conservation"], "cpu", HEADROOM)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", POOL_FWD_CASES + [(POOL_FWD_BIG, "randn")],
+                         ids=lambda c: _pool_id(c) if len(c[0]) == 2 else "big-%s" % c[1])
+def test_maxpool_fwd_edges(hip, case):
+    shape = case[0] if len(case[0]) == 4 else (2, case[0][0], case[0][1], 8)
+    x, ref = pool_fwd_case(shape, case[1])
+    if len(case[0]) == 4:
+        assert ref.numel() // 4 > GRID_CAP
+    _assert_bits("maxpool", str(case), "y", _ops().maxpool3x3s2_nhwc(x.to(DEV)), ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(2, h, w, 8) for h, w in POOL_MAPS] + [POOL_BWD_BIG], ids=lambda s: "%dx%dx%dx%d" % s)
+def test_maxpool_bwd_edges(hip, shape):
+    inp, ref, bars = pool_bwd_case(shape)
+    if shape == POOL_BWD_BIG:
+        assert inp["x"].numel() // 4 > GRID_CAP
+    dx = _ops().maxpool3x3s2_bwd(inp["x"].to(DEV), inp["dy"].to(DEV))
+    _assert_close("maxpool_bwd", str(shape), "dx", dx, ref, bars["dx"], "gpu")
+    _assert_close("maxpool_bwd", str(shape), "conservation", dx.double().sum((0, 1, 2)), inp["dy"].double().sum((0, 1, 2)),
+                  bars["conservation"], "gpu")
+    # each dy lands on a pixel whose value the forward returned: a pixel that received gradient holds the pooled value of one
+    # of the (up to 2 x 2) windows that contain it
+    x = inp["x"]
+    y = F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+    rows = [torch.arange(shape[1]) // 2, ((torch.arange(shape[1]) + 1) // 2).clamp(max=y.shape[1] - 1)]
+    cols = [torch.arange(shape[2]) // 2, ((torch.arange(shape[2]) + 1) // 2).clamp(max=y.shape[2] - 1)]
+    holds = torch.zeros(x.shape, dtype=torch.bool)
+    for r_ in rows:
+        for c_ in cols:
+            holds |= x == y[:, r_][:, :, c_]
+    touched = dx.cpu() != 0
+    assert bool(touched.any()) and bool(holds[touched].all())
+
+
+PAD_CASES = [(35, 1, 4), (35, 3, 4), (35, 3, 8), (35, 4, 4), (525000, 3, 4)]
+
+
+@functools.lru_cache(maxsize=None)
+def pad_case(case):
+    pixels, c, c_pad = case
+    x = torch.randn(1, 1, pixels, c, generator=torch.Generator().manual_seed(600 + c + c_pad)) + 3.0
+    return x, torch.cat((x, torch.zeros(1, 1, pixels, c_pad - c)), 3).contiguous()
+
+
+@pytest.mark.parametrize("case", PAD_CASES, ids=lambda c: "%d-%dto%d" % c)
+def test_cpu_restatement_pad_channels(case):
+    x, ref = pad_case(case)
+    pixels, c, c_pad = case
+    i = np.arange(pixels * c_pad)
+    pix = i // c_pad
+    ch = i - pix * c_pad
+    flat = _np(x).reshape(-1)
+    got = np.where(ch < c, flat[np.minimum(pix * c + ch, flat.size - 1)], f32(0)).astype(f32)
+    _assert_bits("pad", "%d-%dto%d" % case, "y", got.reshape(ref.shape), ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", PAD_CASES, ids=lambda c: "%d-%dto%d" % c)
+def test_pad_channels(hip, case):
+    x, ref = pad_case(case)
+    pixels, c, c_pad = case
+    if pixels > 35:
+        assert pixels * c_pad > GRID_CAP
+    xd = x.to(DEV)
+    out = torch.full((1, 1, pixels, c_pad), -7.0, device=DEV)  # the C ABI: ops.pad_channels returns x itself when c == c_pad
+    rc = hip.frcnn_pad_channels(xd.data_ptr(), out.data_ptr(), pixels, c, c_pad, _stream())
+    assert rc == 0, hip.frcnn_last_error()
+    _assert_bits("pad", "%d-%dto%d" % case, "y", out, ref)
+    _assert_bits("pad", "%d-%dto%d" % case, "y through ops", _ops().pad_channels(xd, c_pad), ref)
+
+
+# ================================================================================================
+# 4. prep_image
+# ================================================================================================
+PREP_MEANS, PREP_STDS = (102.9801, 115.9465, 122.7717), (1.0, 2.0, 0.5)
+ORDERS = list(itertools.permutations((0, 1, 2)))
+PREP_CASES = ([((37, 53), s, (2, 0, 1)) for s in (1.0, 0.5, 0.3, 2.0, 3.7)] + [((37, 53), 1.3, o) for o in ORDERS] +
+              [((1, 1), s, (2, 1, 0)) for s in (1.0, 2.0, 3.7)] + [((1, 40), s, (0, 2, 1)) for s in (1.0, 1.3, 2.0, 3.7)] +
+              [((40, 1), s, (1, 0, 2)) for s in (1.0, 1.3, 2.0, 3.7)] + [((1100, 1000), 1.0, (2, 0, 1))])
+
+
+def _prep_id(c):
+    return "%dx%d-s%s-o%d%d%d" % (c[0] + (repr(c[1]),) + tuple(c[2]))
+
+
+def _scale32(s):
+    return float(f32(s))                                       # the scale travels as a float32 (info[6]); both sides get that value
+
+
+@functools.lru_cache(maxsize=None)
+def prep_case(case):
+    (h, w), s, order = case
+    rng = np.random.default_rng(700 + h + w)
+    im = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    if h * w > 1:                                              # runs of 0 and 255 and a checkerboard next to the noise
+        flat = im.reshape(-1, 3)
+        n = flat.shape[0]
+        flat[: n // 5] = 0
+        flat[n // 5: 2 * n // 5] = 255
+        yy, xx = np.divmod(np.arange(2 * n // 5, 3 * n // 5), w)
+        flat[2 * n // 5: 3 * n // 5] = (((yy + xx) % 2) * 255).astype(np.uint8)[:, None]
+    ref = O.prep_im_for_blob(im, np.array([[PREP_MEANS]]), np.array([[PREP_STDS]]), list(order), _scale32(s))
+    return im, ref, 2e-5 * _big(ref)
+
+
+def _resize_tap32(n_out, inv, size):
+    """resize_tap of csrc/prep.hip: the coordinate in double, rounded once to float32."""
+    f = ((np.arange(n_out, dtype=np.float64) + 0.5) * np.float64(inv) - 0.5).astype(f32)
+    s = np.floor(f).astype(np.int64)
+    f = (f - s.astype(f32)).astype(f32)
+    lo, hi = s < 0, None
+    f[lo], s[lo] = 0, 0
+    hi = s >= size - 1
+    f[hi], s[hi] = 0, size - 1
+    return s, np.minimum(s + 1, size - 1), f32(1) - f, f
+
+
+def prep32(im, scale, order, c_out):
+    h, w = im.shape[:2]
+    ho, wo = int(np.rint(np.float64(h) * np.float64(f32(scale)))), int(np.rint(np.float64(w) * np.float64(f32(scale))))
+    inv = f32(1.0 / np.float64(f32(scale)))
+    x0, x1, a0, a1 = _resize_tap32(wo, inv, w)
+    y0, y1, b0, b1 = _resize_tap32(ho, inv, h)
+    px = im.astype(f32)[:, :, list(order)]
+    a0, a1, b0, b1 = a0[None, :, None], a1[None, :, None], b0[:, None, None], b1[:, None, None]
+    top = px[y0][:, x0] * a0 + px[y0][:, x1] * a1
+    bot = px[y1][:, x0] * a0 + px[y1][:, x1] * a1
+    v = top * b0 + bot * b1
+    centred = (v.astype(np.float64) - np.asarray(PREP_MEANS)).astype(f32)
+    out = np.zeros((ho, wo, c_out), f32)
+    out[:, :, :3] = (centred.astype(np.float64) / np.asarray(PREP_STDS)).astype(f32)
+    return out
+
+
+def _exact_at_scale_1(im, order):
+    return ((im[:, :, list(order)].astype(np.float64) - np.asarray(PREP_MEANS)).astype(f32).astype(np.float64)
+            / np.asarray(PREP_STDS)).astype(f32)
+
+
+@pytest.mark.parametrize("case", PREP_CASES, ids=_prep_id)
+def test_cpu_restatement_prep_image(case):
+    (h, w), s, order = case
+    im, ref, bar = prep_case(case)
+    got = prep32(im, s, order, 4)
+    assert got.shape[:2] == ref.shape[:2] == (int(np.rint(h * _scale32(s))), int(np.rint(w * _scale32(s))))
+    _assert_close("prep", _prep_id(case), "blob", got[:, :, :3], ref, bar, "cpu", HEADROOM)
+    assert (got[:, :, 3] == 0).all()
+    if s == 1.0:
+        _assert_bits("prep", _prep_id(case), "(px - mean) / std", got[:, :, :3], _exact_at_scale_1(im, order))
+    if case[0] == (37, 53) and s == 0.5:
+        assert ref.shape[:2] == (18, 26)                       # 18.5 and 26.5 round to the even neighbour
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", PREP_CASES, ids=_prep_id)
+def test_prep_image_edges(hip, case):
+    from faster_rcnn_pytorch_multimodal_amd.utils.blob import prep_im_for_blob
+    (h, w), s, order = case
+    im, ref, bar = prep_case(case)
+    if h * w > 10000:
+        assert ref.shape[0] * ref.shape[1] > PREP_CAP
+    means, stds = np.array([[PREP_MEANS]]), np.array([[PREP_STDS]])
+    got3 = prep_im_for_blob(im, means, stds, list(order), _scale32(s), pad_to=3, device=DEV)
+    got4 = prep_im_for_blob(im, means, stds, list(order), _scale32(s), pad_to=4, device=DEV)
+    assert tuple(got3.shape) == ref.shape and tuple(got4.shape) == ref.shape[:2] + (4,)
+    _assert_close("prep", _prep_id(case), "blob", got3, ref, bar, "gpu")
+    _assert_bits("prep", _prep_id(case), "c_out 4 vs 3", got4[..., :3].contiguous(), _np(got3))
+    assert bool((got4[..., 3] == 0).all())
+    _assert_bits("prep", _prep_id(case), "restatement", got4, prep32(im, s, order, 4))
+    if s == 1.0:
+        _assert_bits("prep", _prep_id(case), "(px - mean) / std", got3, _exact_at_scale_1(im, order))
+
+
+@pytest.mark.gpu
+def test_prep_image_rejects_an_empty_output(hip):
+    """1 x 40 at 0.5: round-half-even(0.5) = 0 rows.  The C ABI refuses with a message and writes nothing; the Python wrapper,
+    whose zero-row blob has no storage, raises as well."""
+    import ctypes
+    from faster_rcnn_pytorch_multimodal_amd.utils.blob import prep_im_for_blob
+    im = torch.zeros((1, 40, 3), dtype=torch.uint8, device=DEV)
+    blob = torch.full((64,), -7.0, device=DEV)
+    rc = hip.frcnn_prep_image(im.data_ptr(), 1, 40, 0.5, (ctypes.c_double * 3)(*PREP_MEANS), (ctypes.c_double * 3)(*PREP_STDS),
+                              (ctypes.c_int * 3)(0, 1, 2), 3, blob.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    assert rc != 0 and b"empty output" in (hip.frcnn_last_error() or b"") and bool((blob == -7.0).all())
+    with pytest.raises(_hip().HipError, match="prep_image"):
+        prep_im_for_blob(im.cpu().numpy(), np.array([[PREP_MEANS]]), np.array([[PREP_STDS]]), [0, 1, 2], 0.5, device=DEV)
+
+
+# ================================================================================================
+# 5. labelled_pixels / gather_patches / scatter_add_patches
+# ================================================================================================
+LAB_HW, LAB_A = [1, 1023, 1024, 1025, 2500], [1, 9]
+LAB_SETS = ["none", "all-capover", "all-capunder", "last", "edges"]
+LAB_CASES = [(hw, a, s) for hw in LAB_HW for a in LAB_A for s in LAB_SETS]
+
+
+def _lab_id(c):
+    return "hw%d-A%d-%s" % c
+
+
+@functools.lru_cache(maxsize=None)
+def lab_case(case):
+    hw, a, kind = case
+    g = torch.Generator().manual_seed(800 + hw + a)
+    labels = -torch.ones(hw, a)
+    if kind.startswith("all"):
+        on = torch.arange(hw)
+    elif kind == "last":
+        on = torch.tensor([hw - 1])
+    elif kind == "edges":
+        on = torch.tensor(sorted({p for k in range(hw // 1024 + 2) for p in (k * 1024 - 1, k * 1024 + 1) if 0 <= p < hw}),
+                          dtype=torch.int64)
+    else:
+        on = torch.zeros(0, dtype=torch.int64)
+    for p in on.tolist():                                      # one anchor of the pixel carries 0 or 1, the others stay -1
+        labels[p, int(torch.randint(0, a, (1,), generator=g))] = float(torch.randint(0, 2, (1,), generator=g))
+    total = int(on.numel())
+    cap = {"all-capover": hw + 5, "all-capunder": max(1, hw // 2)}.get(kind, 64)
+    want = np.flatnonzero((_np(labels) != -1).any(1))
+    assert want.size == total
+    idx = np.full((cap,), -1, np.int64)
+    idx[:min(total, cap)] = want[:cap]
+    return dict(labels=labels.view(-1).contiguous(), hw=hw, a=a, cap=cap), dict(idx=idx, count=np.array([min(total, cap), total], np.int32))
+
+
+def labelled32(labels, hw, a, cap):
+    """labelled_flags_kernel + labelled_pixels_kernel: passes of 1024 pixels, a running base carried between them."""
+    flag = (labels.reshape(hw, a) != -1).any(1)
+    idx = np.full((cap,), -1, np.int64)
+    base = 0
+    for p0 in range(0, hw, 1024):
+        on = flag[p0:p0 + 1024]
+        pos = base + np.cumsum(on) - on
+        sel = on & (pos < cap)
+        idx[pos[sel]] = p0 + np.flatnonzero(sel)
+        base += int(on.sum())
+    return idx, np.array([min(base, cap), base], np.int32)
+
+
+@pytest.mark.parametrize("case", LAB_CASES, ids=_lab_id)
+def test_cpu_restatement_labelled_pixels(case):
+    inp, ref = lab_case(case)
+    idx, count = labelled32(_np(inp["labels"]), inp["hw"], inp["a"], inp["cap"])
+    _assert_bits("labelled", _lab_id(case), "idx", idx, ref["idx"])
+    _assert_bits("labelled", _lab_id(case), "count", count, ref["count"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", LAB_CASES, ids=_lab_id)
+def test_labelled_pixels_edges(hip, case):
+    inp, ref = lab_case(case)
+    idx, count = _ops().labelled_pixels(inp["labels"].to(DEV), inp["hw"], inp["a"], inp["cap"])
+    _assert_bits("labelled", _lab_id(case), "idx", idx, ref["idx"])
+    _assert_bits("labelled", _lab_id(case), "count", count, ref["count"])
+    live = int(ref["count"][0])
+    got = _np(idx)
+    assert (np.diff(got[:live]) > 0).all() and (got[live:] == -1).all()
+
+
+PATCH_H, PATCH_W, PATCH_C, PATCH_CAP = 5, 7, 8, 8
+PATCH_PIXELS = [0, PATCH_W - 1, (PATCH_H - 1) * PATCH_W, PATCH_H * PATCH_W - 1, 2 * PATCH_W + 3]      # four corners, one interior
+PATCH_FORMS = [(1, 0), (3, 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def patch_case(form, pixels=tuple(PATCH_PIXELS)):
+    r, pad = form
+    g = torch.Generator().manual_seed(900 + r)
+    x = torch.randn(1, PATCH_H, PATCH_W, PATCH_C, generator=g) + 3.0
+    idx = torch.full((PATCH_CAP,), -1, dtype=torch.int64)
+    idx[:len(pixels)] = torch.tensor(pixels)
+    count = torch.tensor([len(pixels), len(pixels)], dtype=torch.int32)
+    xp = F.pad(x[0].permute(2, 0, 1), (pad, pad, pad, pad)).permute(1, 2, 0)
+    ref = torch.zeros(PATCH_CAP, r, r, PATCH_C)
+    for i, p in enumerate(pixels):
+        y, xx = divmod(p, PATCH_W)
+        ref[i] = xp[y:y + r, xx:xx + r]
+    d = torch.randn(PATCH_CAP, r, r, PATCH_C, generator=g)
+    # float64 scatter, and its bar: a pixel receives at most r * r * (pixels) terms by float atomics in any order - T - 1
+    # roundings of U / 2 of the magnitudes added
+    dx = torch.zeros(PATCH_H + 2 * pad, PATCH_W + 2 * pad, PATCH_C, dtype=torch.float64)
+    mag = torch.zeros_like(dx)
+    for i, p in enumerate(pixels):
+        y, xx = divmod(p, PATCH_W)
+        dx[y:y + r, xx:xx + r] += d[i].double()
+        mag[y:y + r, xx:xx + r] += d[i].double().abs()
+    crop = lambda t: t[pad:pad + PATCH_H, pad:pad + PATCH_W].unsqueeze(0).contiguous()
+    terms = r * r * len(pixels)
+    bar_dx = (terms * (U / 2) * crop(mag) + 1e-30).numpy()
+    bars = dict(dx=bar_dx, adjoint=float((x.double().abs().numpy() * bar_dx).sum()))
+    return dict(x=x, idx=idx, count=count, d=d, r=r, pad=pad), dict(patches=ref, dx=crop(dx)), bars
+
+
+OVERLAP_PIXELS = (2 * PATCH_W + 2, 2 * PATCH_W + 3, 2 * PATCH_W + 4, 3 * PATCH_W + 3, 0, 2 * PATCH_W + 3)     # neighbours and a repeat
+
+
+def patches32(inp):
+    x, idx, d = _np(inp["x"])[0], _np(inp["idx"]), _np(inp["d"])
+    r, pad, live = inp["r"], inp["pad"], int(inp["count"][0])
+    out = np.zeros((PATCH_CAP, r, r, PATCH_C), f32)
+    dx = np.zeros((PATCH_H, PATCH_W, PATCH_C), f32)
+    for i in range(live):
+        py, px = divmod(int(idx[i]), PATCH_W)
+        for a in range(r):
+            for b in range(r):
+                y, xx = py + a - pad, px + b - pad
+                if 0 <= y < PATCH_H and 0 <= xx < PATCH_W:
+                    out[i, a, b] = x[y, xx]
+                    dx[y, xx] = dx[y, xx] + d[i, a, b]
+    return out, dx[None]
+
+
+def _patch_cases():
+    return [(f, tuple(PATCH_PIXELS)) for f in PATCH_FORMS] + [((3, 1), OVERLAP_PIXELS)]
+
+
+@pytest.mark.parametrize("case", _patch_cases(), ids=lambda c: "r%d-pad%d-%s" % (c[0] + ("corners" if c[1][0] == 0 else "overlap",)))
+def test_cpu_restatement_patches(case):
+    inp, ref, bars = patch_case(*case)
+    out, dx = patches32(inp)
+    _assert_bits("patches", str(case[0]), "gather", out, ref["patches"])
+    _assert_close("patches", str(case[0]), "scatter", dx, ref["dx"], bars["dx"], "cpu", HEADROOM)
+    lhs = float((out.astype(np.float64) * _np(inp["d"]).astype(np.float64)).sum())
+    rhs = float((_np(inp["x"]).astype(np.float64) * dx.astype(np.float64)).sum())
+    _assert_close("patches", str(case[0]), "adjoint", lhs, rhs, bars["adjoint"], "cpu", HEADROOM)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", _patch_cases(), ids=lambda c: "r%d-pad%d-%s" % (c[0] + ("corners" if c[1][0] == 0 else "overlap",)))
+def test_gather_and_scatter_patches_edges(hip, case):
+    ops = _ops()
+    inp, ref, bars = patch_case(*case)
+    x, idx, count, d = inp["x"].to(DEV), inp["idx"].to(DEV), inp["count"].to(DEV), inp["d"].to(DEV)
+    out = ops.gather_patches(x, idx, count, inp["r"], inp["r"], inp["pad"])
+    _assert_bits("patches", str(case[0]), "gather", out, ref["patches"])
+    assert bool((out[len(case[1]):] == 0).all())
+    dx = ops.scatter_add_patches(d, idx, count, PATCH_H, PATCH_W, inp["pad"])
+    _assert_close("patches", str(case[0]), "scatter", dx, ref["dx"], bars["dx"], "gpu")
+    lhs = float((out.double() * d.double()).sum())
+    rhs = float((x.double() * dx.double()).sum())
+    _assert_close("patches", str(case[0]), "adjoint", lhs, rhs, bars["adjoint"], "gpu")
