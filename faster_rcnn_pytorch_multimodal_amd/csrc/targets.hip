@@ -160,7 +160,10 @@ __global__ __launch_bounds__(256) void atl_label_kernel(const float* __restrict_
   }
 }
 
-// keep[order[i]] = 1 for the first min(count, quota) entries that are real candidates (key > 0)
+// keep[order[i]] = 1 for the first min(count, quota) entries that are real candidates (key > 0).  `top_n` is the number
+// of entries the sort PRODUCED, min(n, quota slots): frcnn_sort_topk_desc writes no more, and with fewer anchors than slots
+// (a 5 x 5 map with 9 anchors against the default 256) the rest of `order` / `sorted_keys` is whatever the reused workspace
+// held - a stale positive key there used to send a stale 64-bit index into keep[].
 __global__ __launch_bounds__(256) void atl_mark_keep_kernel(const int64_t* __restrict__ order,
                                                            const float* __restrict__ sorted_keys, int top_n,
                                                            const int* __restrict__ counters, int which, int quota_total,
@@ -469,11 +472,12 @@ extern "C" int frcnn_anchor_target_layer(const float* anchors, int n, const floa
   const int num_fg_cap = (int)(fg_fraction * (float)rpn_batchsize);   // :91
   if (rpn_batchsize <= 16384) {
     // random sub-sampling: the `quota` candidates with the largest random keys survive
+    const int sorted_n = std::min(n, top_n);   // what the sort writes; the keep scan stops there
     for (int which = 0; which < 2; ++which) {
       rc = frcnn_sort_topk_desc(which == 0 ? key_fg : key_bg, n, top_n, order, sorted, sort_count,
                                 l.sort_ws_bytes ? base + l.sort_ws : nullptr, l.sort_ws_bytes, stream_);
       if (rc != FRCNN_OK) return rc;
-      hipLaunchKernelGGL(atl_mark_keep_kernel, dim3(grid_for((size_t)top_n)), dim3(256), 0, stream, order, sorted, top_n,
+      hipLaunchKernelGGL(atl_mark_keep_kernel, dim3(grid_for((size_t)sorted_n)), dim3(256), 0, stream, order, sorted, sorted_n,
                          counters, which, rpn_batchsize, num_fg_cap, which == 0 ? keep_fg : keep_bg);
       rc = check_launch("atl_mark_keep_kernel");
       if (rc != FRCNN_OK) return rc;
