@@ -21,6 +21,11 @@ ARCH = "gfx950"
 SOURCES = {
     "common.hip": [],
     "conv_igemm.hip": [],
+    "conv_plan.hip": [],
+    "conv_winograd.hip": [],
+    "conv_bf16.hip": [],
+    "conv_dgrad.hip": [],
+    "pool.hip": [],
     "conv_wgrad.hip": [],
     "boxes.hip": ["-ffp-contract=off"],
     "roi_align.hip": ["-ffp-contract=off"],

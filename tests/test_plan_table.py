@@ -24,7 +24,7 @@ from faster_rcnn_pytorch_multimodal_amd import _hip, ops
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 PLANS_PATH = os.path.join(ROOT, "profiles", bench.PLANS_FILE)
 ROWS = json.load(open(PLANS_PATH)) if os.path.exists(PLANS_PATH) else []
-BK = 32                    # K-step of the implicit-GEMM kernels (conv_igemm.hip)
+BK = 32                    # K-step of the implicit-GEMM kernels (conv_common.h)
 RESIDUAL = 256             # key[9] flag: the call has a residual operand
 DEV = "cuda:0"
 INFO = np.array([0, bench.W, 0, bench.H, 0, 0, 1.0], np.float32)
@@ -55,7 +55,7 @@ def _is_fused(row):
 
 
 def _winograd_ws_bytes(n, h, w, c, k):
-    """conv_igemm.hip wino_geom: U (16 K C) | V (16 T C) | M (16 T K) floats, each aligned to 256 bytes."""
+    """conv_winograd.hip wino_geom: U (16 K C) | V (16 T C) | M (16 T K) floats, each aligned to 256 bytes."""
     up = lambda v: -(-v // 256) * 256
     t = n * ((h + 1) // 2) * ((w + 1) // 2)
     return up(16 * k * c * 4) + up(16 * t * c * 4) + up(16 * t * k * 4)

@@ -1,6 +1,6 @@
 """The gather, resampling and compaction kernels between the big ones, at their edges: gather_rows / make_rois
 (csrc/boxes.hip), upsample_bilinear_add_fwd / _bwd (csrc/train_ops.hip), maxpool3x3s2_fwd / _bwd and pad_channels
-(csrc/conv_igemm.hip), prep_image (csrc/prep.hip), labelled_pixels / gather_patches / scatter_add_patches
+(csrc/pool.hip), prep_image (csrc/prep.hip), labelled_pixels / gather_patches / scatter_add_patches
 (csrc/targets.hip).  Each is called directly through ops.py, or through the C ABI where ops.py hides an argument
 (roi_scores == NULL, pad_channels with c == c_pad), and compared with a reference that does not come from the code under
 test: plain indexing for the copies, F.interpolate / F.max_pool2d and their autograd, O.prep_im_for_blob, float64 sums.

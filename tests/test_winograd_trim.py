@@ -1,4 +1,4 @@
-"""Winograd F(2x2, 3x3) without the transform components that feed only dropped outputs (csrc/conv_igemm.hip, wino_geom).
+"""Winograd F(2x2, 3x3) without the transform components that feed only dropped outputs (csrc/conv_winograd.hip, wino_geom).
 
 A map with odd height has a last row of 2x2 output tiles whose second output row lies outside the map; component row i = 3
 of such a tile enters nothing else, and likewise column j = 3 in the last tile column of a map with odd width.  By default

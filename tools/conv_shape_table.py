@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from faster_rcnn_pytorch_multimodal_amd.model.frame_graph import capture  # noqa: E402
 
-TILES = ["256x128", "128x256", "128x128", "128x64", "64x128", "64x64", "128x128d2", "64x64buf", "128x64buf", "64x128buf", "128x128buf", "256x128buf", "128x256buf", "64x64pers"]   # kTiles order (conv_igemm.hip)
+TILES = ["256x128", "128x256", "128x128", "128x64", "64x128", "64x64", "128x128d2", "64x64buf", "128x64buf", "64x128buf", "128x128buf", "256x128buf", "128x256buf", "64x64pers"]   # kTiles order (csrc/conv_igemm.hip)
 BK = 32
 
 

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 code of two builds of one .hip file, kernel by kernel.
+"""Compare the gfx950 code of two builds, kernel by kernel.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function --cuda-device-only -S \
         csrc/conv_igemm.hip -o new.s          (and the same at the other commit -> old.s)
     python tools/isa_diff.py old.s new.s
+    python tools/isa_diff.py old.s -- conv_igemm.s conv_winograd.s conv_bf16.s conv_dgrad.s pool.s
+
+Either side may be several files, the two sides separated by `--` (a unit that was split, or merged): a side is the union
+of its files' kernel symbols, and a symbol that two files of one side define is an error.
 
 For a refactor that must not change code generation.  Per kernel symbol it checks
   * the code-object metadata (VGPR / SGPR / AGPR counts, LDS and scratch bytes, spill counts),
@@ -93,9 +97,29 @@ def classify(a, b):
     return "other"
 
 
+def parse_side(paths):
+    """the union of the kernels of several files; a kernel that two of them define is an error"""
+    bodies, meta = {}, {}
+    for path in paths:
+        b, m = parse(path)
+        twice = sorted((set(b) & set(bodies)) | (set(m) & set(meta)))
+        if twice:
+            sys.exit("%s: defined in another file of the same side too: %s" % (path, twice))
+        bodies.update(b)
+        meta.update(m)
+    return bodies, meta
+
+
 def main():
-    old_b, old_m = parse(sys.argv[1])
-    new_b, new_m = parse(sys.argv[2])
+    args = sys.argv[1:]
+    if "--" in args:
+        olds, news = args[:args.index("--")], args[args.index("--") + 1:]
+    else:
+        olds, news = args[:1], args[1:]
+    if not olds or not news or (("--" not in args) and len(args) != 2):
+        sys.exit(__doc__)
+    old_b, old_m = parse_side(olds)
+    new_b, new_m = parse_side(news)
     bad = False
     if set(old_b) != set(new_b) or set(old_m) != set(new_m):
         print("SYMBOLS DIFFER:", sorted(set(old_b) ^ set(new_b)), sorted(set(old_m) ^ set(new_m)))
