@@ -26,6 +26,7 @@ SOURCES = {
     "conv_bf16.hip": [],
     "conv_dgrad.hip": [],
     "pool.hip": [],
+    "dwconv.hip": ["-ffp-contract=off"],
     "conv_wgrad.hip": [],
     "boxes.hip": ["-ffp-contract=off"],
     "roi_align.hip": ["-ffp-contract=off"],

@@ -82,6 +82,8 @@ def _defaults():
                   GRAPH_MAX_SHAPES=4,      # distinct frame problems held as graphs (least recently used one is dropped)
                   GRAPH_AUTOTUNE=True)     # time the convolution plans of a new frame shape during its warm-up frames
     c.RESNET = dict(MAX_POOL=False, FIXED_BLOCKS=1)
+    # lib/model/config.py:295-308 (nets/mobilenet_v1.py)
+    c.MOBILENET = dict(REGU_DEPTH=False, FIXED_LAYERS=5, WEIGHT_DECAY=0.00004, DEPTH_MULTIPLIER=1.0)
     c.PIXEL_MEANS = np.array([[[96.866, 98.76, 93.85]]])
     c.PIXEL_STDDEVS = np.array([[[1, 1, 1]]])
     c.PIXEL_ARRANGE = [0, 1, 2]

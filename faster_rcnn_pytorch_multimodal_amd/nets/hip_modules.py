@@ -103,6 +103,26 @@ def prepared_conv(conv, bn=None, use_bn=True):
                         refresh=lambda: prepared_conv(conv, bn, use_bn))
 
 
+def prepared_depthwise(conv, bn):
+    """(w_rsc (3,3,C), scale (C,), shift (C,)) of a depthwise 3x3 ``conv`` (groups == C, no bias) with its eval-mode ``bn``
+    folded in, for ``ops.depthwise_conv3x3_nhwc``.  Cached like ``prepared_conv``: storage-stable (a captured frame reads
+    the tensors by address) with a refresh hook (``refresh_derived_weights`` finds it after a weight change)."""
+    c = conv.weight.shape[0]
+    if (conv.groups != c or tuple(conv.weight.shape) != (c, 1, 3, 3) or conv.bias is not None
+            or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1) or tuple(conv.stride) not in ((1, 1), (2, 2))):
+        raise NotImplementedError("prepared_depthwise: not a bias-free 3x3 / pad 1 / stride 1|2 depthwise convolution: %r" % (conv,))
+    stats_version = bn.__dict__.get('_frcnn_stats_version', 0)
+    key = (_versions(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), str(conv.weight.device), stats_version)
+    cache = conv.__dict__.get('_frcnn_prepared_dw')
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    with torch.no_grad():
+        w_rsc = conv.weight.detach().reshape(c, 3, 3).permute(1, 2, 0).contiguous()
+        scale = (bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)).contiguous()
+        shift = (bn.bias.detach() - bn.running_mean.detach() * scale).contiguous()
+    return stable_store(conv, '_frcnn_prepared_dw', key, (w_rsc, scale, shift), refresh=lambda: prepared_depthwise(conv, bn))
+
+
 def prepared_conv_concat(owner, cache_name, parts):
     """Several convolutions that read the SAME input with the same geometry as ONE: ``parts`` = [(conv, bn, use_bn), ...] ->
     (w_krsc (K1 + K2 + .., R, S, C), scale (K,), shift (K,)) with the folded BatchNorm terms concatenated (1 / 0 where a

@@ -567,6 +567,53 @@ def maxpool3x3s2_bwd(x, dy):
     return dx
 
 
+# frcnn_dwconv3x3_fwd: outputs along W one lane produces per work item (include/frcnn_hip.h FRCNN_DWCONV_STRIP)
+DWCONV_STRIP = 4
+
+
+def depthwise_conv3x3_nhwc(x, w_rsc, scale=None, shift=None, stride=1, relu=False, in_cap=float('inf'),
+                           out_cap=float('inf'), out=None):
+    """Depthwise 3x3 / pad 1 convolution with a per-channel affine epilogue (frcnn_dwconv3x3_fwd; MobileNet-v1's conv_dw,
+    lib/nets/mobilenet_v1.py:117-123): x (N,H,W,C), w_rsc (3,3,C), scale / shift (C,) or None ->
+    min(act(conv(min(x, in_cap)) * scale + shift), out_cap), (N,OH,OW,C).  ``out``: a tensor of that shape to write into."""
+    lib = _hip.load()
+    _dev_f32(x, "depthwise_conv3x3_nhwc: x")
+    _dev_f32(w_rsc, "depthwise_conv3x3_nhwc: w_rsc")
+    if x.dim() != 4:
+        raise _hip.HipError("depthwise_conv3x3_nhwc: x must be (N,H,W,C), got %s" % (tuple(x.shape),))
+    n, h, w, c = x.shape
+    if tuple(w_rsc.shape) != (3, 3, c) or w_rsc.device != x.device:
+        raise _hip.HipError("depthwise_conv3x3_nhwc: w_rsc must be (3,3,%d) on %s, got %s" % (c, x.device, tuple(w_rsc.shape)))
+    for t, name in ((scale, "scale"), (shift, "shift")):
+        if t is not None:
+            _dev_f32(t, "depthwise_conv3x3_nhwc: " + name)
+            if tuple(t.shape) != (c,) or t.device != x.device:
+                raise _hip.HipError("depthwise_conv3x3_nhwc: %s must be (%d,) on %s, got %s" % (name, c, x.device, tuple(t.shape)))
+    stride = int(stride)
+    if stride not in (1, 2):
+        raise _hip.HipError("depthwise_conv3x3_nhwc: stride %d (1 or 2)" % stride)
+    shape = (n, (h - 1) // stride + 1, (w - 1) // stride + 1, c)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _dev_f32(out, "depthwise_conv3x3_nhwc: out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _hip.HipError("depthwise_conv3x3_nhwc: out must be %s on %s, got %s" % (shape, x.device, tuple(out.shape)))
+    if n == 0:
+        return out          # an empty tensor has no storage to point at
+    _hip.check(lib.frcnn_dwconv3x3_fwd(_ptr(x), _ptr(w_rsc), _ptr(scale), _ptr(shift), _ptr(out), n, h, w, c, stride,
+                                       float(in_cap), float(out_cap), int(bool(relu)), _stream()), "frcnn_dwconv3x3_fwd")
+    return out
+
+
+def clamp_max_(x, cap):
+    """x = min(x, cap) in place (frcnn_clamp_max): the upper half of a ReLU6 behind a convolution's ReLU epilogue."""
+    lib = _hip.load()
+    _dev_f32(x, "clamp_max_: x")
+    _hip.check(lib.frcnn_clamp_max(_ptr(x), x.numel(), float(cap), _stream()), "frcnn_clamp_max")
+    return x
+
+
 def pad_channels(x, c_pad):
     """(N,H,W,C) -> (N,H,W,c_pad) zero-padded channels."""
     lib = _hip.load()

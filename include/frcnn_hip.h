@@ -261,6 +261,26 @@ int frcnn_maxpool3x3s2_fwd(const float* x, float* y, int n, int h, int w, int c,
  * maximum (row-major scan, like the index torch stores) is that pixel; gather form, deterministic. */
 int frcnn_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int n, int h, int w, int c, void* stream);
 
+/* Depthwise 3x3 convolution, pad 1, stride 1 or 2, with the folded BatchNorm and ReLU6 of MobileNet-v1's conv_dw block:
+ * nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False) -> nn.BatchNorm2d (eval) -> nn.ReLU6
+ * (lib/nets/mobilenet_v1.py:117-123).  x (n,h,w,c) NHWC, w_rsc (3,3,c) (the module's (c,1,3,3) weight, channel last),
+ * y (n,oh,ow,c) with oh = (h-1)/stride + 1, ow likewise.  Per output element
+ *   acc = sum over the taps inside the image of w_rsc[r,s,ch] * min(x[n, oh*stride-1+r, ow*stride-1+s, ch], in_cap)
+ *   t = acc * scale[ch] + shift[ch]   (null scale / shift: 1 / 0);   t = max(t, 0) if relu;   y = min(t, out_cap).
+ * Zero padding is per image.  in_cap finishes the ReLU6 of the layer that produced x (its kernel applied max(.,0) only),
+ * out_cap = 6 with relu = 1 is this layer's own ReLU6; +inf switches a cap off.  What a NaN in x or t becomes under a
+ * cap is not pinned.  fp32, products and sums rounded one by one (no fma), taps added in a fixed order: deterministic.
+ * FRCNN_ERR_ARG without a launch: c % 4 != 0, stride outside {1,2}, n < 0, h / w / c < 1, c > 262144, a null x / w_rsc /
+ * y, a pointer that is not 16-byte aligned.  n == 0: FRCNN_OK, nothing launched.  One launch, no workspace.
+ * FRCNN_DWCONV_STRIP: outputs along W one lane produces per work item (widths around its multiples are the kernel's edges). */
+#define FRCNN_DWCONV_STRIP 4
+int frcnn_dwconv3x3_fwd(const float* x, const float* w_rsc, const float* scale, const float* shift, float* y, int n, int h,
+                        int w, int c, int stride, float in_cap, float out_cap, int relu, void* stream);
+/* x[i] = min(x[i], cap) in place over count floats: the upper half of an nn.ReLU6 (lib/nets/mobilenet_v1.py:115,131)
+ * whose lower half ran in a convolution's epilogue, for the two pointwise outputs no depthwise layer reads.  What a NaN
+ * becomes is not pinned.  count == 0: nothing launched.  FRCNN_ERR_ARG: count < 0, null x, x not 16-byte aligned. */
+int frcnn_clamp_max(float* x, int64_t count, float cap, void* stream);
+
 /* NHWC image/BEV blob (lib/roi_data_layer/minibatch.py:670 layout, (1,H,W,C)) -> NHWC with the channel
  * count padded with zeros to c_pad (multiple of 4) so the stem conv reads 16-byte pixels. */
 int frcnn_pad_channels(const float* x, float* y, int64_t pixels, int c, int c_pad, void* stream);
