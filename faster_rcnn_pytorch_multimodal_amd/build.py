@@ -27,6 +27,7 @@ SOURCES = {
     "conv_dgrad.hip": [],
     "pool.hip": [],
     "dwconv.hip": ["-ffp-contract=off"],
+    "dwconv_bwd.hip": ["-ffp-contract=off"],
     "conv_wgrad.hip": [],
     "boxes.hip": ["-ffp-contract=off"],
     "roi_align.hip": ["-ffp-contract=off"],

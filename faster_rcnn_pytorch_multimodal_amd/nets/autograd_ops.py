@@ -1,7 +1,8 @@
 """Autograd nodes of the training path (``Network.train_step`` -> ``loss.backward()``,
 lib/model/train_val.py:458): each node's forward AND backward are libfrcnn_hip.so launches
 (``frcnn_conv2d_fwd / _bwd_data / _bwd_weight``, ``frcnn_act_bwd``, ``frcnn_upsample_bilinear_*``,
-``frcnn_roi_align_fwd / _bwd``, ``frcnn_rpn_loss``, ``frcnn_det_loss``).  torch.autograd only orders the nodes
+``frcnn_roi_align_fwd / _bwd``, ``frcnn_rpn_loss``, ``frcnn_det_loss``, and for MobileNet-v1 ``frcnn_dwconv3x3_fwd /
+_bwd_data / _bwd_weight`` and ``frcnn_act_bwd_cap``).  torch.autograd only orders the nodes
 and owns the ``.grad`` buffers; gradient accumulation inside a residual block is fused into the data-gradient
 kernel's epilogue (``add=``), so a Bottleneck is ONE node.
 
@@ -17,7 +18,7 @@ import os
 import torch
 
 from .. import ops
-from .hip_modules import _winograd_filter, pad4, prepared_conv, stable_store
+from .hip_modules import _winograd_filter, pad4, prepared_conv, prepared_depthwise, stable_store
 
 
 # How one pass launches its filter gradients.  They are off the critical path of backward (only the data gradient feeds the next
@@ -193,6 +194,7 @@ def _transposed_filter(conv_like, w_krsc):
                         refresh=lambda: _transposed_filter(conv_like, w_krsc))[0]
 
 
+RELU6_CAP = 6.0                 # nn.ReLU6 of MobileNet-v1 (_SeparablePairFn)
 FUSE_ACT_BWD = True             # False: a separate frcnn_act_bwd pass after each data gradient inside a Bottleneck
 DGRAD_WINOGRAD_CACHE = True     # False: the data-gradient convolution transforms its filter on every call
 
@@ -569,6 +571,67 @@ def bottleneck_train(x, block):
     if block.downsample is not None:
         weights.append(block.downsample[0].weight)
     return _BottleneckFn.apply(x, block, block.batchnorm_en, *weights)
+
+
+class _SeparablePairFn(torch.autograd.Function):
+    """One depthwise-separable child of MobileNet-v1 (lib/nets/mobilenet_v1.py:117-132) as one node, BatchNorms frozen and
+    folded: a = relu6(bn(dw(min(x, in_cap)))), b = relu(bn(pw(a))) with b's upper clamp PENDING - the next child reads
+    min(b, 6) through its ``in_cap`` - unless ``finish_cap``: then the node applies it in place (Conv2d_11, read by the RPN
+    and the RoIAlign; Conv2d_13, read by the spatial mean).  Either way the incoming gradient is the one with respect to
+    min(b, 6), and 0 < b < 6 is the ReLU6 mask whether or not b has been clamped."""
+
+    @staticmethod
+    def forward(ctx, x, pair, in_cap, finish_cap, dw_weight, pw_weight):
+        dw, pw = pair.depthwise[0], pair.pointwise[0]
+        wd, sd, bd = prepared_depthwise(dw, pair.depthwise[1])
+        wp, sp, bp = prepared_conv(pw, pair.pointwise[1], True)
+        stride = dw.stride[0]
+        a = ops.depthwise_conv3x3_nhwc(x, wd, sd, bd, stride=stride, relu=True, in_cap=in_cap, out_cap=RELU6_CAP)
+        b = ops.conv2d_nhwc(a, wp, sp, bp, None, stride=1, pad=0, relu=True)
+        if finish_cap:
+            ops.clamp_max_(b, RELU6_CAP)
+        ctx.pair = pair
+        ctx.meta = (wd, sd, wp, sp, stride, in_cap)
+        ctx.save_for_backward(x, a, b)
+        return b
+
+    @staticmethod
+    def backward(ctx, db):
+        x, a, b = ctx.saved_tensors
+        dw, pw = ctx.pair.depthwise[0], ctx.pair.pointwise[0]
+        wd, sd, wp, sp, stride, in_cap = ctx.meta
+        need_x, need_dw, need_pw = ctx.needs_input_grad[0], ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        d_pw = ops.act_bwd_cap(db.contiguous(), b, sp, relu=True, cap=RELU6_CAP)
+        g_pw = _wgrad(a, d_pw, 1, 1, 1, 0, pw.weight)[0] if need_pw else None
+        dx = g_dw = None
+        if need_x or need_dw:
+            da = ops.conv2d_bwd_data(d_pw, _transposed_filter(pw, wp), tuple(a.shape))
+            if need_dw:
+                def filter_grad(out=None, accumulate=False):
+                    return ops.depthwise_conv3x3_bwd_weight(x, da, a, sd, stride=stride, relu=True, in_cap=in_cap,
+                                                            out_cap=RELU6_CAP, out=out, accumulate=accumulate)
+                grad = dw.weight.grad
+                if not SCHEDULE.accumulate:
+                    g_dw = filter_grad()
+                elif grad is not None and grad.is_contiguous():
+                    # the kernel's own second launch adds into param.grad: no permute, no add_ launch
+                    _launch_wgrad(grad, [x, da, a], lambda: filter_grad(grad, True))
+                else:
+                    _launch_wgrad(dw.weight, [x, da, a], lambda: _accumulate(dw.weight, filter_grad()))
+            if need_x:
+                dx = ops.depthwise_conv3x3_bwd_data(da, a, wd, tuple(x.shape), sd, stride=stride, relu=True, out_cap=RELU6_CAP)
+        return dx, None, None, None, g_dw, g_pw
+
+
+def separable_pair_train(x, pair, in_cap, finish_cap):
+    """Differentiable depthwise-separable child; ``x`` NHWC with the upper clamp ``in_cap`` pending (inf: none)."""
+    for bn in (pair.depthwise[1], pair.pointwise[1]):
+        if bn.training:
+            raise NotImplementedError("BatchNorm in training mode (batch statistics) is not on the HIP path yet")
+        if any(p.requires_grad for p in bn.parameters()):
+            raise NotImplementedError("trainable BatchNorm affine parameters with frozen (eval-mode) statistics are not on "
+                                      "the HIP path: the reference either freezes both or trains both")
+    return _SeparablePairFn.apply(x, pair, float(in_cap), bool(finish_cap), pair.depthwise[0].weight, pair.pointwise[0].weight)
 
 
 class _MaxPoolFn(torch.autograd.Function):

@@ -1,4 +1,4 @@
-"""MobileNet-v1 detector for inference - counterpart of the reference's lib/nets/mobilenet_v1.py (``--net mobile``).
+"""MobileNet-v1 detector - counterpart of the reference's lib/nets/mobilenet_v1.py (``--net mobile``).
 
 Body (mobilenet_v1.py:33-49, 107-132): ``Conv2d_0`` is a 3x3 / stride 2 / pad 1 convolution 3 -> 32 with BatchNorm and
 ReLU6; ``Conv2d_1`` .. ``Conv2d_13`` are pairs of a ``depthwise`` 3x3 (groups == C, pad 1) and a ``pointwise`` 1x1
@@ -13,13 +13,21 @@ kernels apply the lower half, the upper clamp is applied by the reader of the va
 (``in_cap=6``), or one ``ops.clamp_max_`` behind ``Conv2d_11`` (net_conv: read by the RPN and the RoIAlign) and behind
 ``Conv2d_13`` (read by the spatial mean).
 
-Inference only: a ``mode='TRAIN'`` forward raises (the depthwise gradients and the ReLU6 mask are not built).
+Training is opt-in: ``cfg.TRAIN.MOBILENET_EN`` (default False).  While it is off a ``mode='TRAIN'`` forward raises as an
+inference-only net does.  With it on, children below ``cfg.MOBILENET.FIXED_LAYERS`` (1..12; the stem ``Conv2d_0`` cannot
+train: its GEMM reads a 3-channel input padded to 4) keep the inference path and save nothing, and every other child is ONE
+autograd node (``autograd_ops.separable_pair_train``): its backward is ``ops.act_bwd_cap`` (the pointwise ReLU6 mask), the
+GEMM filter and data gradients of the pointwise layer, and ``ops.depthwise_conv3x3_bwd_weight / _bwd_data``, which apply
+the depthwise ReLU6 mask as they load.  The upper clamps behind ``Conv2d_11`` and ``Conv2d_13`` run inside their nodes.
+BatchNorm stays frozen and folded.  Eager and captured steps (``enable_train_graphs``) both work.
 """
+import torch
 import torch.nn as nn
 
 from .. import ops
 from ..model.config import cfg
 from ..utils.init_utils import normal_init, set_bn_eval, set_bn_fix
+from .autograd_ops import separable_pair_train, spatial_mean_train
 from .hip_modules import conv_bn_act, prepared_depthwise, to_nchw_view, to_nhwc
 from .network import Network
 
@@ -56,12 +64,24 @@ def _is_conv(m):
     return m.__class__.__name__.find('Conv') != -1
 
 
-def run_children(x, children, in_cap):
+def train_enabled():
+    return bool(cfg.TRAIN.get('MOBILENET_EN', False))
+
+
+def run_children(x, children, in_cap, train=False, finish=False):
     """Walk body children on an NHWC tensor.  ``in_cap``: the pending upper clamp of ``x`` (6 behind a GEMM convolution,
     inf for a finished tensor).  The result's upper clamp is PENDING when the last child ended in a GEMM convolution -
-    all of them do."""
-    for child in children:
+    all of them do - unless ``finish``: then the last child's ReLU6 is completed (in place).
+    ``train``: a child with a trainable parameter, or behind one, runs as one autograd node; the others run the inference
+    path and save nothing."""
+    children = list(children)
+    for i, child in enumerate(children):
+        last = finish and i == len(children) - 1
         if hasattr(child, 'depthwise'):
+            if train and (x.requires_grad or any(p.requires_grad for p in child.parameters())):
+                x = separable_pair_train(x, child, in_cap, finish_cap=last)
+                in_cap = RELU6_CAP
+                continue
             conv, bn = child.depthwise[0], child.depthwise[1]
             if bn.training:
                 raise NotImplementedError("BatchNorm in training mode (batch statistics) is not on the HIP path yet")
@@ -71,9 +91,18 @@ def run_children(x, children, in_cap):
             x = conv_bn_act(x, child.pointwise[0], child.pointwise[1], relu=True)
         else:
             assert in_cap == float('inf'), "Conv2d_0 reads the image"
+            if train and any(p.requires_grad for p in child.parameters()):
+                raise NotImplementedError(STEM_NOT_TRAINABLE)
             x = conv_bn_act(x, child[0], child[1], relu=True)
+        if last:
+            x = ops.clamp_max_(x, RELU6_CAP)
         in_cap = RELU6_CAP
     return x
+
+
+STEM_NOT_TRAINABLE = ("cfg.MOBILENET.FIXED_LAYERS = 0: the stem Conv2d_0 cannot train on the HIP path - its GEMM convolution "
+                      "reads the 3-channel image padded to 4 channels, which the differentiable convolution does not take; "
+                      "FIXED_LAYERS 1..12 are supported")
 
 
 class mobilenetv1(Network):
@@ -145,21 +174,31 @@ class mobilenetv1(Network):
 
     def forward(self, image, info, gt_boxes=None, gt_boxes_dc=None, mode='TRAIN'):
         if mode != 'TEST':
-            raise NotImplementedError("mobilenetv1.forward(mode=%r): inference only - the depthwise data and filter "
-                                      "gradients and the ReLU6 mask are not built" % (mode,))
+            if not train_enabled():
+                raise NotImplementedError("mobilenetv1.forward(mode=%r): inference only while cfg.TRAIN.MOBILENET_EN is False "
+                                          "(set it to run the depthwise data and filter gradients and the ReLU6 masks)" % (mode,))
+            if cfg.MOBILENET.FIXED_LAYERS < 1:
+                raise NotImplementedError(STEM_NOT_TRAINABLE)
         return Network.forward(self, image, info, gt_boxes, gt_boxes_dc, mode=mode)
 
     def _image_to_head(self):
         self._pyramid = None
-        x = run_children(to_nhwc(self._image), self._layers['head'], float('inf'))
-        net_conv = ops.clamp_max_(x, RELU6_CAP)          # Conv2d_11's ReLU6: the RPN and the RoIAlign read it as it is
+        # finish: Conv2d_11's ReLU6 is completed - the RPN and the RoIAlign read net_conv as it is
+        net_conv = run_children(to_nhwc(self._image), self._layers['head'], float('inf'), train=self._training_pass(),
+                                finish=True)
         self._act_summaries['conv'] = net_conv
         return to_nchw_view(net_conv)
 
     _input_to_head = _image_to_head
 
     def _head_to_tail(self, pool5):
-        if getattr(self, '_mode', 'TEST') != 'TEST':
-            raise NotImplementedError("mobilenetv1._head_to_tail: inference only")
-        x = run_children(to_nhwc(pool5), self._layers['tail'], float('inf'))
-        return self._fc7_from_layer4(ops.clamp_max_(x, RELU6_CAP))      # Conv2d_13's ReLU6, then mean + detection tail
+        if getattr(self, '_mode', 'TEST') != 'TEST' and not train_enabled():
+            raise NotImplementedError("mobilenetv1._head_to_tail: inference only while cfg.TRAIN.MOBILENET_EN is False")
+        # finish: Conv2d_13's ReLU6 is completed in front of the mean
+        x = run_children(to_nhwc(pool5), self._layers['tail'], float('inf'), train=self._training_pass(), finish=True)
+        if self._training_pass():
+            return spatial_mean_train(x)
+        return self._fc7_from_layer4(x)                  # mean + detection tail
+
+    def _training_pass(self):
+        return getattr(self, '_mode', 'TEST') == 'TRAIN' and torch.is_grad_enabled() and train_enabled()

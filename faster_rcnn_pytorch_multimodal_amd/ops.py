@@ -614,6 +614,111 @@ def clamp_max_(x, cap):
     return x
 
 
+def _dw_bwd_operands(who, dy, y, scale, x_shape, stride, relu, out_cap):
+    """Argument checks shared by the two depthwise gradients: dy (and y, scale) against the INPUT shape (N,H,W,C)."""
+    _dev_f32(dy, who + ": dy")
+    if len(x_shape) != 4:
+        raise _hip.HipError("%s: x must be (N,H,W,C), got %s" % (who, tuple(x_shape)))
+    n, h, w, c = (int(v) for v in x_shape)
+    stride = int(stride)
+    if stride not in (1, 2):
+        raise _hip.HipError("%s: stride %d (1 or 2)" % (who, stride))
+    shape = (n, (h - 1) // stride + 1, (w - 1) // stride + 1, c)
+    if tuple(dy.shape) != shape:
+        raise _hip.HipError("%s: dy must be %s for x %s at stride %d, got %s" % (who, shape, (n, h, w, c), stride, tuple(dy.shape)))
+    if y is not None:
+        _dev_f32(y, who + ": y")
+        if tuple(y.shape) != shape or y.device != dy.device:
+            raise _hip.HipError("%s: y must be %s on %s, got %s" % (who, shape, dy.device, tuple(y.shape)))
+    elif relu or float(out_cap) != float('inf'):
+        raise _hip.HipError("%s: y is needed for the mask of relu / out_cap" % who)
+    if scale is not None:
+        _dev_f32(scale, who + ": scale")
+        if tuple(scale.shape) != (c,) or scale.device != dy.device:
+            raise _hip.HipError("%s: scale must be (%d,) on %s, got %s" % (who, c, dy.device, tuple(scale.shape)))
+    return n, h, w, c, stride
+
+
+def depthwise_conv3x3_bwd_data(dy, y, w_rsc, x_shape, scale=None, stride=1, relu=False, out_cap=float('inf'), out=None):
+    """Data gradient of ``depthwise_conv3x3_nhwc`` (frcnn_dwconv3x3_bwd_data; lib/nets/mobilenet_v1.py:117-123 under
+    loss.backward()): dy, y (N,OH,OW,C) - y the forward's stored output, None when neither relu nor out_cap masks -,
+    w_rsc (3,3,C) -> the gradient (N,H,W,C) with respect to min(x, in_cap).  ``out``: a tensor of that shape to write into."""
+    lib = _hip.load()
+    who = "depthwise_conv3x3_bwd_data"
+    n, h, w, c, stride = _dw_bwd_operands(who, dy, y, scale, x_shape, stride, relu, out_cap)
+    _dev_f32(w_rsc, who + ": w_rsc")
+    if tuple(w_rsc.shape) != (3, 3, c) or w_rsc.device != dy.device:
+        raise _hip.HipError("%s: w_rsc must be (3,3,%d) on %s, got %s" % (who, c, dy.device, tuple(w_rsc.shape)))
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=dy.device)
+    else:
+        _dev_f32(out, who + ": out")
+        if tuple(out.shape) != (n, h, w, c) or out.device != dy.device:
+            raise _hip.HipError("%s: out must be %s on %s, got %s" % (who, (n, h, w, c), dy.device, tuple(out.shape)))
+    if n == 0:
+        return out
+    _hip.check(lib.frcnn_dwconv3x3_bwd_data(_ptr(dy), _ptr(y), _ptr(w_rsc), _ptr(scale), _ptr(out), n, h, w, c, stride,
+                                            float(out_cap), int(bool(relu)), _stream()), "frcnn_dwconv3x3_bwd_data")
+    return out
+
+
+def depthwise_conv3x3_bwd_weight(x, dy, y, scale=None, stride=1, relu=False, in_cap=float('inf'), out_cap=float('inf'),
+                                 out=None, accumulate=False):
+    """Filter gradient of ``depthwise_conv3x3_nhwc`` in the parameter's own (C,1,3,3) layout (frcnn_dwconv3x3_bwd_weight):
+    x (N,H,W,C) the forward's input, dy / y (N,OH,OW,C).  ``out``: the buffer to write; ``accumulate``: add into it (a
+    parameter's ``.grad``) instead of overwriting.  Deterministic: two calls on the same operands are bit-equal."""
+    lib = _hip.load()
+    who = "depthwise_conv3x3_bwd_weight"
+    _dev_f32(x, who + ": x")
+    n, h, w, c, stride = _dw_bwd_operands(who, dy, y, scale, tuple(x.shape), stride, relu, out_cap)
+    if x.device != dy.device:
+        raise _hip.HipError("%s: x on %s, dy on %s" % (who, x.device, dy.device))
+    if out is None:
+        if accumulate:
+            raise _hip.HipError("%s: accumulate needs out=" % who)
+        out = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=x.device)
+    else:
+        _dev_f32(out, who + ": out")
+        if tuple(out.shape) != (c, 1, 3, 3) or out.device != x.device:
+            raise _hip.HipError("%s: out must be (%d,1,3,3) on %s, got %s" % (who, c, x.device, tuple(out.shape)))
+    if n == 0:              # an empty tensor has no storage to point at: the sum over no pixels
+        return out if accumulate else out.zero_()
+    ws_bytes = lib.frcnn_dwconv3x3_bwd_weight_ws_bytes(n, h, w, c, stride)
+    ws = _workspace(ws_bytes, x.device)
+    _hip.check(lib.frcnn_dwconv3x3_bwd_weight(_ptr(x), _ptr(dy), _ptr(y), _ptr(scale), _ptr(out), n, h, w, c, stride,
+                                              float(in_cap), float(out_cap), int(bool(relu)), int(bool(accumulate)), _ptr(ws),
+                                              ws_bytes, _stream()), "frcnn_dwconv3x3_bwd_weight")
+    return out
+
+
+def act_bwd_cap(dy, y, scale=None, relu=True, cap=float('inf'), out=None):
+    """Backward of a ReLU6 behind a GEMM convolution (frcnn_act_bwd_cap): dy * scale[k] * [y > 0 if relu] * [y < cap],
+    k = dy.shape[-1]; ``y`` is the convolution's stored output, with or without the upper clamp applied."""
+    lib = _hip.load()
+    _dev_f32(dy, "act_bwd_cap: dy")
+    k = dy.shape[-1] if dy.dim() else 1
+    masked = bool(relu) or float(cap) != float('inf')
+    if masked or y is not None:
+        _dev_f32(y, "act_bwd_cap: y")
+        if tuple(y.shape) != tuple(dy.shape) or y.device != dy.device:
+            raise _hip.HipError("act_bwd_cap: y must be %s on %s, got %s" % (tuple(dy.shape), dy.device, tuple(y.shape)))
+    if scale is not None:
+        _dev_f32(scale, "act_bwd_cap: scale")
+        if tuple(scale.shape) != (k,) or scale.device != dy.device:
+            raise _hip.HipError("act_bwd_cap: scale must be (%d,) on %s, got %s" % (k, dy.device, tuple(scale.shape)))
+    if out is None:
+        out = torch.empty_like(dy)
+    else:
+        _dev_f32(out, "act_bwd_cap: out")
+        if tuple(out.shape) != tuple(dy.shape) or out.device != dy.device:
+            raise _hip.HipError("act_bwd_cap: out must be %s on %s, got %s" % (tuple(dy.shape), dy.device, tuple(out.shape)))
+    if dy.numel() == 0:
+        return out
+    _hip.check(lib.frcnn_act_bwd_cap(_ptr(dy), _ptr(y), _ptr(scale), int(bool(relu)), float(cap), dy.numel() // k, k, _ptr(out),
+                                     _stream()), "frcnn_act_bwd_cap")
+    return out
+
+
 def pad_channels(x, c_pad):
     """(N,H,W,C) -> (N,H,W,c_pad) zero-padded channels."""
     lib = _hip.load()

@@ -281,6 +281,41 @@ int frcnn_dwconv3x3_fwd(const float* x, const float* w_rsc, const float* scale, 
  * becomes is not pinned.  count == 0: nothing launched.  FRCNN_ERR_ARG: count < 0, null x, x not 16-byte aligned. */
 int frcnn_clamp_max(float* x, int64_t count, float cap, void* stream);
 
+/* Gradients of the depthwise convolution above, for training MobileNet-v1: what autograd runs for
+ * lib/nets/mobilenet_v1.py:117-123 under loss.backward() (lib/model/train_val.py:458).  In the forward's notation
+ * u = min(x, in_cap), t = conv(u) * scale + shift, y = min(relu ? max(t, 0) : t, out_cap), both read the MASKED upstream
+ * gradient, computed from dy and the forward's stored y as they are loaded and never stored:
+ *   dz[n,oh,ow,ch] = dy[n,oh,ow,ch] * scale[ch] * m,   m = 1 where (relu off or y > 0) and y < out_cap, else 0
+ * (hardtanh's backward as torch defines it for nn.ReLU6: zero at both closed ends).  With relu = 0 and out_cap = +inf the
+ * mask is 1 and y may be null; a null scale is 1.  fp32, products and sums rounded one by one, fixed order, no atomics:
+ * two runs on the same operands are bit-equal.  Argument rules as the forward's (FRCNN_ERR_ARG without a launch: c % 4,
+ * stride outside {1,2}, n < 0, h / w / c < 1, a null required pointer, a null y with a mask, a pointer that is not 16-byte
+ * aligned); n == 0: FRCNN_OK.
+ *
+ * bwd_data: the gradient with respect to u, (n,h,w,c):
+ *   dx[n,hh,ww,ch] = sum over (r,s) with (hh+1-r), (ww+1-s) divisible by stride and inside (oh,ow) of
+ *                    w_rsc[r,s,ch] * dz[n,(hh+1-r)/stride,(ww+1-s)/stride,ch]
+ * Gather form, every element of dx written once.  The ReLU6 mask of the layer that produced x (in_cap) belongs to that
+ * layer's backward; x is not read.  One launch, no workspace.
+ *
+ * bwd_weight: the parameter's own (c,1,3,3) layout,
+ *   dw[ch,0,r,s] (+)= sum over n,oh,ow of dz[n,oh,ow,ch] * min(x[n,oh*stride-1+r,ow*stride-1+s,ch], in_cap)
+ * (taps outside the image contribute 0); accumulate = 1 adds into dw, 0 overwrites (n == 0: dw is zeroed).  Two launches:
+ * workgroup partials into ws (the _ws_bytes query, 16-byte aligned), then their sum in a fixed order. */
+int frcnn_dwconv3x3_bwd_data(const float* dy, const float* y, const float* w_rsc, const float* scale, float* dx, int n, int h,
+                             int w, int c, int stride, float out_cap, int relu, void* stream);
+size_t frcnn_dwconv3x3_bwd_weight_ws_bytes(int n, int h, int w, int c, int stride);
+int frcnn_dwconv3x3_bwd_weight(const float* x, const float* dy, const float* y, const float* scale, float* dw, int n, int h,
+                               int w, int c, int stride, float in_cap, float out_cap, int relu, int accumulate, void* ws,
+                               size_t ws_bytes, void* stream);
+/* Backward of a ReLU6 behind a GEMM convolution (the pointwise layers, lib/nets/mobilenet_v1.py:117-123 under
+ * loss.backward(), lib/model/train_val.py:458): d_conv = dy * scale[k] * [y > 0 if relu] * [y < cap] over rows x k floats,
+ * any k >= 1.  The convolution's stored y carries the lower half of the ReLU6 only; 0 < y < cap is the same mask whether or
+ * not the upper clamp has been applied to y in place.  Null scale: 1; null y only with relu = 0 and cap = +inf.
+ * rows * k == 0: nothing launched.  FRCNN_ERR_ARG: rows < 0, k < 1, a null dy / d_conv, a pointer not 16-byte aligned. */
+int frcnn_act_bwd_cap(const float* dy, const float* y, const float* scale, int relu, float cap, int64_t rows, int k,
+                      float* d_conv, void* stream);
+
 /* NHWC image/BEV blob (lib/roi_data_layer/minibatch.py:670 layout, (1,H,W,C)) -> NHWC with the channel
  * count padded with zeros to c_pad (multiple of 4) so the stem conv reads 16-byte pixels. */
 int frcnn_pad_channels(const float* x, float* y, int64_t pixels, int c, int c_pad, void* stream);
