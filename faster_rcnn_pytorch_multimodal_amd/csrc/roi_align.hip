@@ -1,4 +1,4 @@
-// RoIAlign forward, torchvision 0.4.0 semantics (aligned=False), NHWC in / NHWC out.
+// RoIAlign forward and backward, torchvision 0.4.0 semantics (aligned=False), NHWC in / NHWC out.
 // Reference call sites: lib/utils/torchpoolers.py:165-170,194-197 (roi_align) and the 'align' pooling of
 // the missing network.py (_crop_pool_layer; POOLING_MODE lib/model/config.py:364).
 //
@@ -38,6 +38,64 @@ struct RoiEpilogue {
   }
 };
 
+// What a RoI row (batch index, x1, y1, x2, y2) means on the map, torchvision 0.4.0's expressions in its order.  Every kernel
+// form below evaluates it through this one function, so all of them sample the same float32 coordinates bit for bit.
+struct RoiGeom {
+  int b;                       // image the RoI belongs to (the row's batch column)
+  float start_w, start_h;      // first sampled column / row
+  float bin_w, bin_h;          // size of one of the P x P bins
+  int grid_w, grid_h;          // samples per bin and axis
+};
+
+__device__ __forceinline__ RoiGeom roi_geom(const float* __restrict__ roi, float spatial_scale, int P, int sampling_ratio) {
+  RoiGeom g;
+  g.b = (int)roi[0];
+  g.start_w = roi[1] * spatial_scale;
+  g.start_h = roi[2] * spatial_scale;
+  const float roi_end_w = roi[3] * spatial_scale;
+  const float roi_end_h = roi[4] * spatial_scale;
+  const float roi_width = fmaxf(roi_end_w - g.start_w, 1.0f);
+  const float roi_height = fmaxf(roi_end_h - g.start_h, 1.0f);
+  g.bin_h = roi_height / (float)P;
+  g.bin_w = roi_width / (float)P;
+  g.grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_height / (float)P);
+  g.grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_width / (float)P);
+  return g;
+}
+
+// Sample i of bin pbin along one axis: its two pixels and their weights; false = the sample lies outside [-1, size] and
+// is dropped.
+__device__ __forceinline__ bool axis_sample_pt(float start, float bin_size, int pbin, int i, int grid, int size, int& lo,
+                                               int& hi, float& wlo, float& whi) {
+  float v = start + pbin * bin_size + ((float)i + .5f) * bin_size / (float)grid;
+  if (v < -1.0f || v > (float)size) return false;
+  if (v <= 0.f) v = 0.f;
+  lo = (int)v;
+  if (lo >= size - 1) { hi = lo = size - 1; v = (float)lo; } else hi = lo + 1;
+  whi = v - (float)lo;
+  wlo = 1.f - whi;
+  return true;
+}
+
+// The samples of bin (ph, pw) in the library's order (rows outside, columns inside), empty samples dropped:
+// f(y_low, y_high, x_low, x_high, w1, w2, w3, w4), the weights of (low, low), (low, high), (high, low), (high, high).
+// The two sample-by-sample kernels walk a bin through it.  The map-resident kernel's path for oversized bins keeps the same
+// two loops over axis_sample_pt written out: routed through here, the scheduling of its row loop changes.
+template <class F>
+__device__ __forceinline__ void for_each_sample(const RoiGeom& g, int ph, int pw, int H, int W, F&& f) {
+  for (int iy = 0; iy < g.grid_h; ++iy) {
+    int yl, yh;
+    float hy, ly;
+    if (!axis_sample_pt(g.start_h, g.bin_h, ph, iy, g.grid_h, H, yl, yh, hy, ly)) continue;
+    for (int ix = 0; ix < g.grid_w; ++ix) {
+      int xl, xh;
+      float hx, lx;
+      if (!axis_sample_pt(g.start_w, g.bin_w, pw, ix, g.grid_w, W, xl, xh, hx, lx)) continue;
+      f(yl, yh, xl, xh, hy * hx, hy * lx, ly * hx, ly * lx);
+    }
+  }
+}
+
 // XCD_SPLIT: workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share one), so workgroup b works on
 // channel slice b % 8 only: each XCD's private 4 MB L2 then holds 1/8 of the feature map (1.2 MB of the 9.8 MB
 // res101 map) instead of thrashing on all of it — the PMC passes showed 127 MB fetched from beyond L2 per launch
@@ -69,47 +127,56 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc(const float* __restric
     if (level_of_roi && level_of_roi[r] != level) continue;  // another level writes this roi
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < live) {
-      const float* roi = rois + (size_t)r * 5;
-      const int b = (int)roi[0];
-      const float roi_start_w = roi[1] * spatial_scale;
-      const float roi_start_h = roi[2] * spatial_scale;
-      const float roi_end_w = roi[3] * spatial_scale;
-      const float roi_end_h = roi[4] * spatial_scale;
-      const float roi_width = fmaxf(roi_end_w - roi_start_w, 1.0f);
-      const float roi_height = fmaxf(roi_end_h - roi_start_h, 1.0f);
-      const float bin_size_h = roi_height / (float)P;
-      const float bin_size_w = roi_width / (float)P;
-      const int grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_height / (float)P);
-      const int grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_width / (float)P);
-      const float count = (float)(grid_h * grid_w);
-      const float4* fb = reinterpret_cast<const float4*>(feat) + (size_t)b * H * W * C4 + c4;
-      for (int iy = 0; iy < grid_h; ++iy) {
-        float y = roi_start_h + ph * bin_size_h + ((float)iy + .5f) * bin_size_h / (float)grid_h;
-        for (int ix = 0; ix < grid_w; ++ix) {
-          float x = roi_start_w + pw * bin_size_w + ((float)ix + .5f) * bin_size_w / (float)grid_w;
-          float yy = y;
-          if (yy < -1.0f || yy > (float)H || x < -1.0f || x > (float)W) continue;  // empty sample
-          if (yy <= 0.f) yy = 0.f;
-          if (x <= 0.f) x = 0.f;
-          int y_low = (int)yy, x_low = (int)x, y_high, x_high;
-          if (y_low >= H - 1) { y_high = y_low = H - 1; yy = (float)y_low; } else y_high = y_low + 1;
-          if (x_low >= W - 1) { x_high = x_low = W - 1; x = (float)x_low; } else x_high = x_low + 1;
-          const float ly = yy - (float)y_low, lx = x - (float)x_low;
-          const float hy = 1.f - ly, hx = 1.f - lx;
-          const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-          const float4 v1 = fb[((size_t)y_low * W + x_low) * C4];
-          const float4 v2 = fb[((size_t)y_low * W + x_high) * C4];
-          const float4 v3 = fb[((size_t)y_high * W + x_low) * C4];
-          const float4 v4 = fb[((size_t)y_high * W + x_high) * C4];
-          acc.x += w1 * v1.x + w2 * v2.x + w3 * v3.x + w4 * v4.x;
-          acc.y += w1 * v1.y + w2 * v2.y + w3 * v3.y + w4 * v4.y;
-          acc.z += w1 * v1.z + w2 * v2.z + w3 * v3.z + w4 * v4.z;
-          acc.w += w1 * v1.w + w2 * v2.w + w3 * v3.w + w4 * v4.w;
-        }
-      }
+      const RoiGeom g = roi_geom(rois + (size_t)r * 5, spatial_scale, P, sampling_ratio);
+      const float count = (float)(g.grid_h * g.grid_w);
+      const float4* fb = reinterpret_cast<const float4*>(feat) + (size_t)g.b * H * W * C4 + c4;
+      for_each_sample(g, ph, pw, H, W, [&](int y_low, int y_high, int x_low, int x_high, float w1, float w2, float w3,
+                                           float w4) {
+        const float4 v1 = fb[((size_t)y_low * W + x_low) * C4];
+        const float4 v2 = fb[((size_t)y_low * W + x_high) * C4];
+        const float4 v3 = fb[((size_t)y_high * W + x_low) * C4];
+        const float4 v4 = fb[((size_t)y_high * W + x_high) * C4];
+        acc.x += w1 * v1.x + w2 * v2.x + w3 * v3.x + w4 * v4.x;
+        acc.y += w1 * v1.y + w2 * v2.y + w3 * v3.y + w4 * v4.y;
+        acc.z += w1 * v1.z + w2 * v2.z + w3 * v3.z + w4 * v4.z;
+        acc.w += w1 * v1.w + w2 * v2.w + w3 * v3.w + w4 * v4.w;
+      });
       acc.x /= count; acc.y /= count; acc.z /= count; acc.w /= count;
     }
     reinterpret_cast<float4*>(out)[item] = epi.apply(acc, c4);
+  }
+}
+
+// Backward of the kernel above (torchvision roi_align autograd, aligned=False): one thread per (bin, channel); every sample
+// scatters dout / count * bilinear weight onto its four pixels with float atomics.  dfeat must be zero-filled.
+__global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restrict__ dout, int H, int W, int C,
+                                                         const float* __restrict__ rois,
+                                                         const int* __restrict__ roi_count, int num_rois, int P,
+                                                         float spatial_scale, int sampling_ratio,
+                                                         const int* __restrict__ level_of_roi, int level,
+                                                         float* __restrict__ dfeat) {
+  const int live = roi_count ? min(*roi_count, num_rois) : num_rois;
+  const size_t total = (size_t)num_rois * P * P * C;
+  for (size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x; item < total;
+       item += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(item % C);
+    size_t bin = item / C;
+    const int pw = (int)(bin % P);
+    bin /= P;
+    const int ph = (int)(bin % P);
+    const int r = (int)(bin / P);
+    if (r >= live) continue;
+    if (level_of_roi && level_of_roi[r] != level) continue;
+    const RoiGeom g = roi_geom(rois + (size_t)r * 5, spatial_scale, P, sampling_ratio);
+    const float gr = dout[item] / (float)(g.grid_h * g.grid_w);
+    float* fb = dfeat + (size_t)g.b * H * W * C + c;
+    for_each_sample(g, ph, pw, H, W, [&](int y_low, int y_high, int x_low, int x_high, float w1, float w2, float w3,
+                                         float w4) {
+      atomicAdd(fb + ((size_t)y_low * W + x_low) * C, gr * w1);
+      atomicAdd(fb + ((size_t)y_low * W + x_high) * C, gr * w2);
+      atomicAdd(fb + ((size_t)y_high * W + x_low) * C, gr * w3);
+      atomicAdd(fb + ((size_t)y_high * W + x_high) * C, gr * w4);
+    });
   }
 }
 
@@ -151,18 +218,6 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc(const float* __restric
 // without pipelining: 31 us (a wave lived 12 us on average, 31 us at worst: per-item latency chain x imbalance).
 // ------------------------------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool axis_sample_pt(float start, float bin_size, int pbin, int i, int grid, int size, int& lo,
-                                               int& hi, float& wlo, float& whi) {
-  float v = start + pbin * bin_size + ((float)i + .5f) * bin_size / (float)grid;
-  if (v < -1.0f || v > (float)size) return false;
-  if (v <= 0.f) v = 0.f;
-  lo = (int)v;
-  if (lo >= size - 1) { hi = lo = size - 1; v = (float)lo; } else hi = lo + 1;
-  whi = v - (float)lo;
-  wlo = 1.f - whi;
-  return true;
-}
 
 __device__ __forceinline__ float lane_bcast(float v, int lane) {   // lane is wave-uniform
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -235,19 +290,13 @@ __global__ __launch_bounds__(64 * 2 * PLAN_P) void roi_plan_kernel(int H, int W,
   float inv_count = 0.f;
   int bimg = 0;
   if (flag == ROI_LIGHT || flag == ROI_HEAVY) {
-    const float* roi = rois + (size_t)r * 5;
-    bimg = (int)roi[0];
-    const float roi_start_w = roi[1] * spatial_scale, roi_start_h = roi[2] * spatial_scale;
-    const float roi_end_w = roi[3] * spatial_scale, roi_end_h = roi[4] * spatial_scale;
-    const float roi_width = fmaxf(roi_end_w - roi_start_w, 1.0f), roi_height = fmaxf(roi_end_h - roi_start_h, 1.0f);
-    const float bin_size_h = roi_height / (float)P, bin_size_w = roi_width / (float)P;
-    const int grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_height / (float)P);
-    const int grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_width / (float)P);
-    inv_count = 1.0f / (float)(grid_h * grid_w);
+    const RoiGeom g = roi_geom(rois + (size_t)r * 5, spatial_scale, P, sampling_ratio);
+    bimg = g.b;
+    inv_count = 1.0f / (float)(g.grid_h * g.grid_w);
     const bool is_x = wave < P;
     const int bin = is_x ? wave : wave - P;
-    const float start = is_x ? roi_start_w : roi_start_h, bin_size = is_x ? bin_size_w : bin_size_h;
-    const int grid = __builtin_amdgcn_readfirstlane(is_x ? grid_w : grid_h), size = is_x ? W : H;
+    const float start = is_x ? g.start_w : g.start_h, bin_size = is_x ? g.bin_w : g.bin_h;
+    const int grid = __builtin_amdgcn_readfirstlane(is_x ? g.grid_w : g.grid_h), size = is_x ? W : H;
     float* table = is_x ? wxt + ((size_t)r * P + bin) * plan_pad(W) : wyt + ((size_t)r * P + bin) * plan_pad(H);
     // lane-parallel sample evaluation; invalid -> NO_PIXEL
     auto sample = [&](int i, int& lo, int& hi, float& wl, float& wh) {
@@ -713,12 +762,8 @@ __global__ __launch_bounds__(64 * RES_WAVES) void roi_align_fwd_resident(
       if (lvl_ok && dead) state = (img == 0 || rois_per_image > 0) ? ST_ZERO : ST_SKIP;
       else if (lvl_ok && (rois_per_image > 0 || bimg == img)) {
         state = ST_TABLE;
-        rsw = roi[1] * spatial_scale; rsh = roi[2] * spatial_scale;
-        const float rew = roi[3] * spatial_scale, reh = roi[4] * spatial_scale;
-        const float roi_width = fmaxf(rew - rsw, 1.0f), roi_height = fmaxf(reh - rsh, 1.0f);
-        bh = roi_height / (float)P; bw = roi_width / (float)P;
-        gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_height / (float)P);
-        gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_width / (float)P);
+        const RoiGeom g = roi_geom(roi, spatial_scale, P, sampling_ratio);
+        rsw = g.start_w; rsh = g.start_h; bw = g.bin_w; bh = g.bin_h; gw = g.grid_w; gh = g.grid_h;
         inv_count = 1.0f / (float)(gh * gw);
         if (gw > 16 || gh > 16) state = ST_DIRECT;
       }
@@ -881,10 +926,30 @@ __global__ __launch_bounds__(64 * RES_WAVES) void roi_align_fwd_resident(
   }
 }
 
+// The plan workspace: head | items[num_rois * P * slices] | wxt[num_rois * P * pad(w)] | wyt[num_rois * P * pad(h)].
+// slices = item descriptors per piece: one per 256-channel slice, or 1 for a plan shared by launches over channel ranges.
+struct PlanBuffers {
+  RoiPlanHead* head;
+  RoiItem* items;
+  float* wxt;
+  float* wyt;
+  int slices;
+  size_t bytes;                   // what the workspace has to hold
+};
+
+int plan_slices_of(int c) { return (c / 4 + 63) / 64; }
+
+PlanBuffers plan_buffers(void* ws, int h, int w, int num_rois, int slices) {
+  const size_t bins = (size_t)num_rois * PLAN_P;
+  const size_t items_at = sizeof(RoiPlanHead), wxt_at = items_at + bins * slices * sizeof(RoiItem);
+  const size_t wyt_at = wxt_at + bins * plan_pad(w) * sizeof(float), end = wyt_at + bins * plan_pad(h) * sizeof(float);
+  const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
+  return {reinterpret_cast<RoiPlanHead*>(base), reinterpret_cast<RoiItem*>(base + items_at),
+          reinterpret_cast<float*>(base + wxt_at), reinterpret_cast<float*>(base + wyt_at), slices, end};
+}
+
 size_t plan_bytes(int h, int w, int c, int num_rois) {
-  const int nslices = (c / 4 + 63) / 64;
-  return sizeof(RoiPlanHead) + (size_t)num_rois * PLAN_P * nslices * sizeof(RoiItem) +
-         (size_t)num_rois * PLAN_P * (plan_pad(w) + plan_pad(h)) * sizeof(float);
+  return plan_buffers(nullptr, h, w, num_rois, plan_slices_of(c)).bytes;
 }
 
 bool planned_ok(int pooled) { return pooled == PLAN_P; }
@@ -914,6 +979,35 @@ unsigned long long frcnn::roi_settings_word() {
 
 static bool resident_ok(int h, int w, int c, int pooled) {
   return pooled == PLAN_P && c % 16 == 0 && h <= 64 && w <= 1024 && res_lds_bytes(h, w) <= (size_t)160 * 1024;
+}
+
+static int launch_plan(const PlanBuffers& pb, int h, int w, const float* rois, const int* roi_count, int num_rois,
+                       float spatial_scale, int sampling_ratio, const int* level_of_roi, int level, hipStream_t stream) {
+  hipLaunchKernelGGL(roi_plan_kernel, dim3((unsigned)num_rois), dim3(64 * 2 * PLAN_P), 0, stream, h, w, rois, roi_count,
+                     num_rois, spatial_scale, sampling_ratio, level_of_roi, level, pb.slices, g_roi_heavy_loads, pb.head,
+                     pb.items, pb.wxt, pb.wyt);
+  return frcnn::check_launch("roi_plan_kernel");
+}
+
+// Persistent grid of the planned kernels: 4-wave workgroups, as many as are resident at once (workgroups_per_cu x 256 CUs),
+// never more waves than wave-items in the worst case, and a multiple of nslices so that a workgroup keeps its slice.
+static unsigned planned_grid(int num_rois, int nslices, int workgroups_per_cu) {
+  const long max_wave_items = (long)num_rois * nslices * PLAN_P * PLAN_P;
+  const long nwg = std::min<long>(256L * workgroups_per_cu, (max_wave_items + 3) / 4);
+  return (unsigned)std::max<long>(nslices, nwg / nslices * nslices);
+}
+
+// roi_align_fwd_planned<g8 ? 8 : 4, epi_form> over float4 groups [off4, off4 + c4) of a map with s4 groups per pixel
+static int launch_planned(bool g8, bool epi_form, unsigned nwg, const float* feat, int h, int w, int c4, int s4, int off4,
+                          const PlanBuffers& pb, float* out, const RoiEpilogue& epi, hipStream_t stream) {
+  auto launch = [&](auto g_tag, auto epi_tag) {
+    hipLaunchKernelGGL((roi_align_fwd_planned<decltype(g_tag)::value, decltype(epi_tag)::value>), dim3(nwg), dim3(256), 0,
+                       stream, feat, h, w, c4, s4, off4, pb.slices, (c4 + 63) / 64, pb.head, pb.items, pb.wxt, pb.wyt, out,
+                       epi);
+  };
+  auto with_epi = [&](auto g_tag) { epi_form ? launch(g_tag, std::true_type{}) : launch(g_tag, std::false_type{}); };
+  g8 ? with_epi(std::integral_constant<int, 8>{}) : with_epi(std::integral_constant<int, 4>{});
+  return frcnn::check_launch("roi_align_fwd_planned");
 }
 
 extern "C" size_t frcnn_roi_align_fwd_ws_bytes(int h, int w, int c, int num_rois, int pooled) {
@@ -960,37 +1054,15 @@ extern "C" int frcnn_roi_align_fwd_affine(const float* feat, int n, int h, int w
   FRCNN_REQUIRE(rois_per_image == 0 || n == 1, "roi_align_fwd: per-image RoI blocks need the map-resident kernel");
   const bool want_planned = g_roi_variant == 0 || g_roi_variant == 3 || g_roi_variant == 4;
   if (want_planned && planned_ok(pooled) && ws && ws_bytes >= plan_bytes(h, w, c, num_rois)) {
-    const int c4 = c / 4, nslices = (c4 + 63) / 64;
-    RoiPlanHead* head = static_cast<RoiPlanHead*>(ws);
-    RoiItem* items = reinterpret_cast<RoiItem*>(head + 1);
-    float* wxt = reinterpret_cast<float*>(items + (size_t)num_rois * PLAN_P * nslices);
-    float* wyt = wxt + (size_t)num_rois * PLAN_P * plan_pad(w);
-    hipLaunchKernelGGL(roi_plan_kernel, dim3((unsigned)num_rois), dim3(64 * 2 * PLAN_P), 0, stream, h, w, rois, roi_count,
-                       num_rois, spatial_scale, sampling_ratio, level_of_roi, level, nslices, g_roi_heavy_loads, head, items, wxt,
-                       wyt);
-    int rc = frcnn::check_launch("roi_plan_kernel");
+    const PlanBuffers pb = plan_buffers(ws, h, w, num_rois, plan_slices_of(c));
+    const int rc = launch_plan(pb, h, w, rois, roi_count, num_rois, spatial_scale, sampling_ratio, level_of_roi, level,
+                               stream);
     if (rc != FRCNN_OK) return rc;
-    // persistent grid of 4-wave workgroups, as many as are resident at once: 88 VGPRs with 4 loads in flight per lane =
-    // 5 waves per SIMD = 5 workgroups per CU (measured best: 22.9 us; 8 loads in flight need 104 VGPRs = 4 per CU: 25.5 us).  A multiple of nslices so that a workgroup keeps its slice;
-    // never more waves than wave-items in the worst case
-    const long max_wave_items = (long)num_rois * nslices * PLAN_P * PLAN_P;
-    const bool g8 = g_roi_variant == 3;                  // variant 3: 8 loads in flight (104 VGPRs, 4 workgroups per CU)
-    long nwg = 256 * ((g8 || has_epi) ? 4 : 5);      // the epilogue form holds 108 VGPRs: 4 waves per SIMD
-    nwg = std::min(nwg, (max_wave_items + 3) / 4);
-    nwg = std::max<long>(nslices, nwg / nslices * nslices);
-    if (!g8 && !has_epi)
-      hipLaunchKernelGGL((roi_align_fwd_planned<4, false>), dim3((unsigned)nwg), dim3(256), 0, stream, feat, h, w, c4, c4, 0, nslices, nslices,
-                         head, items, wxt, wyt, out, epi);
-    else if (!g8)
-      hipLaunchKernelGGL((roi_align_fwd_planned<4, true>), dim3((unsigned)nwg), dim3(256), 0, stream, feat, h, w, c4, c4, 0, nslices, nslices,
-                         head, items, wxt, wyt, out, epi);
-    else if (!has_epi)
-      hipLaunchKernelGGL((roi_align_fwd_planned<8, false>), dim3((unsigned)nwg), dim3(256), 0, stream, feat, h, w, c4, c4, 0, nslices, nslices,
-                         head, items, wxt, wyt, out, epi);
-    else
-      hipLaunchKernelGGL((roi_align_fwd_planned<8, true>), dim3((unsigned)nwg), dim3(256), 0, stream, feat, h, w, c4, c4, 0, nslices, nslices,
-                         head, items, wxt, wyt, out, epi);
-    return frcnn::check_launch("roi_align_fwd_planned");
+    // 88 VGPRs with 4 loads in flight per lane = 5 waves per SIMD = 5 workgroups per CU (measured best: 22.9 us); variant 3,
+    // 8 loads in flight, needs 104 VGPRs and the epilogue form holds 108: 4 per CU (25.5 us)
+    const bool g8 = g_roi_variant == 3;
+    return launch_planned(g8, has_epi, planned_grid(num_rois, pb.slices, (g8 || has_epi) ? 4 : 5), feat, h, w, c / 4, c / 4,
+                          0, pb, out, epi, stream);
   }
   const size_t total = (size_t)num_rois * pooled * pooled * (c / 4);
   if (g_roi_variant != 1 && c % 32 == 0) {   // 8 channel slices of c/8 channels, one per XCD; grid = multiple of 8
@@ -1030,28 +1102,16 @@ extern "C" int frcnn_roi_align_fwd_split(const float* feat, int h, int w, int c,
   if (!ws || ws_bytes < plan_bytes(h, w, 4, num_rois))
     return frcnn::fail(FRCNN_ERR_WS, "roi_align_fwd_split: workspace %zu < %zu bytes", ws_bytes, plan_bytes(h, w, 4, num_rois));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  RoiPlanHead* head = static_cast<RoiPlanHead*>(ws);
-  RoiItem* items = reinterpret_cast<RoiItem*>(head + 1);
-  float* wxt = reinterpret_cast<float*>(items + (size_t)num_rois * PLAN_P);
-  float* wyt = wxt + (size_t)num_rois * PLAN_P * plan_pad(w);
-  hipLaunchKernelGGL(roi_plan_kernel, dim3((unsigned)num_rois), dim3(64 * 2 * PLAN_P), 0, stream, h, w, rois, roi_count,
-                     num_rois, spatial_scale, sampling_ratio, (const int*)nullptr, -1, 1, g_roi_heavy_loads, head, items, wxt, wyt);
-  int rc = frcnn::check_launch("roi_plan_kernel");
-  if (rc != FRCNN_OK) return rc;
+  const PlanBuffers pb = plan_buffers(ws, h, w, num_rois, 1);
+  int rc = launch_plan(pb, h, w, rois, roi_count, num_rois, spatial_scale, sampling_ratio, nullptr, -1, stream);
   const int s4 = c / 4;
-  for (int part = 0; part < 2; ++part) {
+  for (int part = 0; part < 2 && rc == FRCNN_OK; ++part) {
     const int off4 = part == 0 ? 0 : split_c / 4, c4 = part == 0 ? split_c / 4 : s4 - split_c / 4;
-    const int nslices = (c4 + 63) / 64;
     const RoiEpilogue epi{scale ? scale + 4 * off4 : nullptr, shift ? shift + 4 * off4 : nullptr, part == 0 ? relu1 : relu2};
-    const long max_wave_items = (long)num_rois * nslices * PLAN_P * PLAN_P;
-    long nwg = std::min<long>(256 * 4, (max_wave_items + 3) / 4);
-    nwg = std::max<long>(nslices, nwg / nslices * nslices);
-    hipLaunchKernelGGL((roi_align_fwd_planned<4, true>), dim3((unsigned)nwg), dim3(256), 0, stream, feat, h, w, c4, s4, off4, 1,
-                       nslices, head, items, wxt, wyt, part == 0 ? out1 : out2, epi);
-    rc = frcnn::check_launch("roi_align_fwd_planned");
-    if (rc != FRCNN_OK) return rc;
+    rc = launch_planned(false, true, planned_grid(num_rois, (c4 + 63) / 64, 4), feat, h, w, c4, s4, off4, pb,
+                        part == 0 ? out1 : out2, epi, stream);
   }
-  return FRCNN_OK;
+  return rc;
 }
 
 // Backward through the plan (see roi_align_bwd_planned): dfeat (n,H,W,C) += scatter(dout (R,P,P,C)); dfeat is zero-filled
@@ -1066,20 +1126,24 @@ extern "C" int frcnn_roi_align_bwd_planned(const float* dout, int h, int w, int 
   if (!ws || ws_bytes < plan_bytes(h, w, c, num_rois))
     return frcnn::fail(FRCNN_ERR_WS, "roi_align_bwd_planned: workspace %zu < %zu bytes", ws_bytes, plan_bytes(h, w, c, num_rois));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int c4 = c / 4, nslices = (c4 + 63) / 64;
-  RoiPlanHead* head = static_cast<RoiPlanHead*>(ws);
-  RoiItem* items = reinterpret_cast<RoiItem*>(head + 1);
-  float* wxt = reinterpret_cast<float*>(items + (size_t)num_rois * PLAN_P * nslices);
-  float* wyt = wxt + (size_t)num_rois * PLAN_P * plan_pad(w);
-  hipLaunchKernelGGL(roi_plan_kernel, dim3((unsigned)num_rois), dim3(64 * 2 * PLAN_P), 0, stream, h, w, rois, roi_count,
-                     num_rois, spatial_scale, sampling_ratio, level_of_roi, level, nslices, g_roi_heavy_loads, head, items, wxt,
-                     wyt);
-  int rc = frcnn::check_launch("roi_plan_kernel");
+  const PlanBuffers pb = plan_buffers(ws, h, w, num_rois, plan_slices_of(c));
+  const int rc = launch_plan(pb, h, w, rois, roi_count, num_rois, spatial_scale, sampling_ratio, level_of_roi, level,
+                             stream);
   if (rc != FRCNN_OK) return rc;
-  const long max_wave_items = (long)num_rois * nslices * PLAN_P * PLAN_P;
-  long nwg = std::min<long>(256 * 5, (max_wave_items + 3) / 4);
-  nwg = std::max<long>(nslices, nwg / nslices * nslices);
-  hipLaunchKernelGGL(roi_align_bwd_planned, dim3((unsigned)nwg), dim3(256), 0, stream, dout, h, w, c4, nslices, head, items,
-                     wxt, wyt, dfeat);
+  hipLaunchKernelGGL(roi_align_bwd_planned, dim3(planned_grid(num_rois, pb.slices, 5)), dim3(256), 0, stream, dout, h, w,
+                     c / 4, pb.slices, pb.head, pb.items, pb.wxt, pb.wyt, dfeat);
   return frcnn::check_launch("roi_align_bwd_planned");
+}
+
+// The same gradient sample by sample (see roi_align_bwd_nhwc): any pooled size and channel count.
+extern "C" int frcnn_roi_align_bwd(const float* dout, int h, int w, int c, const float* rois, const int* roi_count,
+                                   int num_rois, int pooled, float spatial_scale, int sampling_ratio,
+                                   const int* level_of_roi, int level, float* dfeat, void* stream_) {
+  FRCNN_REQUIRE(dout && rois && dfeat && h > 0 && w > 0 && c > 0 && num_rois > 0 && pooled > 0,
+                "roi_align_bwd: bad arguments");
+  const size_t total = (size_t)num_rois * pooled * pooled * c;
+  const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
+  hipLaunchKernelGGL(roi_align_bwd_nhwc, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), dout, h, w,
+                     c, rois, roi_count, num_rois, pooled, spatial_scale, sampling_ratio, level_of_roi, level, dfeat);
+  return frcnn::check_launch("roi_align_bwd_nhwc");
 }

@@ -1,7 +1,7 @@
 // Training-path kernels other than the convolutions: activation backward, FPN bilinear upsample-add
-// (forward/backward), RoIAlign backward, the RPN / detection losses with their gradients.
+// (forward/backward), the RPN / detection losses with their gradients (RoIAlign's backward: roi_align.hip).
 // HBM/latency-bound elementwise and gather work: 16-byte accesses along the channel dimension, wave-uniform
-// sampling weights, fixed-order reductions (the only non-deterministic pieces are the float-atomic scatters: RoIAlign backward, patch gradients).
+// sampling weights, fixed-order reductions (the only non-deterministic piece is the float-atomic scatter of the patch gradients).
 // Built with -ffp-contract=off: the reference evaluates these expressions as separate torch ops.
 #include "common.h"
 #include "box_math.h"
@@ -119,59 +119,6 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
       }
     }
     reinterpret_cast<f32x4*>(dx)[i] = acc;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// RoIAlign backward (torchvision roi_align autograd, aligned=False): every sample scatters
-// dout/count * bilinear weight onto its four pixels with float atomics.  dfeat must be zero-filled.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restrict__ dout, int H, int W, int C,
-                                                         const float* __restrict__ rois,
-                                                         const int* __restrict__ roi_count, int num_rois, int P,
-                                                         float spatial_scale, int sampling_ratio,
-                                                         const int* __restrict__ level_of_roi, int level,
-                                                         float* __restrict__ dfeat) {
-  const int live = roi_count ? min(*roi_count, num_rois) : num_rois;
-  const size_t total = (size_t)num_rois * P * P * C;
-  for (size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x; item < total;
-       item += (size_t)gridDim.x * blockDim.x) {
-    const int c = (int)(item % C);
-    size_t bin = item / C;
-    const int pw = (int)(bin % P);
-    bin /= P;
-    const int ph = (int)(bin % P);
-    const int r = (int)(bin / P);
-    if (r >= live) continue;
-    if (level_of_roi && level_of_roi[r] != level) continue;
-    const float* roi = rois + (size_t)r * 5;
-    const int b = (int)roi[0];
-    const float roi_start_w = roi[1] * spatial_scale, roi_start_h = roi[2] * spatial_scale;
-    const float roi_end_w = roi[3] * spatial_scale, roi_end_h = roi[4] * spatial_scale;
-    const float roi_width = fmaxf(roi_end_w - roi_start_w, 1.0f), roi_height = fmaxf(roi_end_h - roi_start_h, 1.0f);
-    const float bin_size_h = roi_height / (float)P, bin_size_w = roi_width / (float)P;
-    const int grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_height / (float)P);
-    const int grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_width / (float)P);
-    const float g = dout[item] / (float)(grid_h * grid_w);
-    float* fb = dfeat + (size_t)b * H * W * C + c;
-    for (int iy = 0; iy < grid_h; ++iy) {
-      const float y0 = roi_start_h + ph * bin_size_h + ((float)iy + .5f) * bin_size_h / (float)grid_h;
-      for (int ix = 0; ix < grid_w; ++ix) {
-        float x = roi_start_w + pw * bin_size_w + ((float)ix + .5f) * bin_size_w / (float)grid_w;
-        float y = y0;
-        if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) continue;
-        if (y <= 0.f) y = 0.f;
-        if (x <= 0.f) x = 0.f;
-        int y_low = (int)y, x_low = (int)x, y_high, x_high;
-        if (y_low >= H - 1) { y_high = y_low = H - 1; y = (float)y_low; } else y_high = y_low + 1;
-        if (x_low >= W - 1) { x_high = x_low = W - 1; x = (float)x_low; } else x_high = x_low + 1;
-        const float ly = y - (float)y_low, lx = x - (float)x_low, hy = 1.f - ly, hx = 1.f - lx;
-        atomicAdd(fb + ((size_t)y_low * W + x_low) * C, g * (hy * hx));
-        atomicAdd(fb + ((size_t)y_low * W + x_high) * C, g * (hy * lx));
-        atomicAdd(fb + ((size_t)y_high * W + x_low) * C, g * (ly * hx));
-        atomicAdd(fb + ((size_t)y_high * W + x_high) * C, g * (ly * lx));
-      }
-    }
   }
 }
 
@@ -447,18 +394,6 @@ extern "C" int frcnn_upsample_bilinear_bwd(const float* dout, float* dx, int n, 
   hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream_), dout, n,
                      h, w, out_h, out_w, c / 4, dx);
   return check_launch("upsample_bwd_kernel");
-}
-
-extern "C" int frcnn_roi_align_bwd(const float* dout, int h, int w, int c, const float* rois, const int* roi_count,
-                                   int num_rois, int pooled, float spatial_scale, int sampling_ratio,
-                                   const int* level_of_roi, int level, float* dfeat, void* stream_) {
-  FRCNN_REQUIRE(dout && rois && dfeat && h > 0 && w > 0 && c > 0 && num_rois > 0 && pooled > 0,
-                "roi_align_bwd: bad arguments");
-  const size_t total = (size_t)num_rois * pooled * pooled * c;
-  hipLaunchKernelGGL(roi_align_bwd_nhwc, dim3(grid_for(total, 1u << 20)), dim3(256), 0, static_cast<hipStream_t>(stream_),
-                     dout, h, w, c, rois, roi_count, num_rois, pooled, spatial_scale, sampling_ratio, level_of_roi, level,
-                     dfeat);
-  return check_launch("roi_align_bwd_nhwc");
 }
 
 extern "C" size_t frcnn_rpn_loss_ws_bytes(void) { return (size_t)LOSS_BLOCKS * 3 * sizeof(float); }

@@ -922,34 +922,36 @@ def make_rois(sorted_boxes, sorted_scores, keep_idx, keep_count):
     return rois, roi_scores
 
 
+def _roi_epilogue_and_plan(who, lib, feat, r, pooled, plan_c, scale, shift):
+    """What the RoIAlign forwards share: checks the optional per-channel ``scale`` / ``shift`` against feat's channels and
+    returns the plan workspace ``(ws, ws_bytes)`` of a map with ``plan_c`` channels; ws is None when pooled has no plan."""
+    _, h, w, c = feat.shape
+    for nm, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _dev_f32(t, nm)
+            if t.numel() != c:
+                raise _hip.HipError("%s: %s has %d elements, expected %d" % (who, nm, t.numel(), c))
+    ws_bytes = lib.frcnn_roi_align_fwd_ws_bytes(h, w, plan_c, r, pooled)
+    return (_workspace(ws_bytes, feat.device) if ws_bytes else None), ws_bytes
+
+
 def roi_align_nhwc(feat, rois, pooled, spatial_scale, sampling_ratio=0, roi_count=None, level_of_roi=None, level=-1,
                    out=None, rois_per_image=0, scale=None, shift=None, relu=False):
     """feat (N,H,W,C), rois (R,5) -> (R, P, P, C).  ``rois_per_image`` > 0: rows [i*rpi, (i+1)*rpi) belong to image i and
     ``roi_count`` holds N live counts (frames batched into one call); 0: the image is the RoI's batch column.
     ``scale`` / ``shift`` (C,) / ``relu``: per-channel epilogue on the pooled values, out = act(pooled * scale + shift)
-    (frcnn_roi_align_fwd_affine)."""
+    (frcnn_roi_align_fwd_affine; without them it is what frcnn_roi_align_fwd computes)."""
     lib = _hip.load()
     _dev_f32(feat, "feat"); _dev_f32(rois, "rois")
     n, h, w, c = feat.shape
     r = rois.shape[0]
-    for nm, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _dev_f32(t, nm)
-            if t.numel() != c:
-                raise _hip.HipError("roi_align_nhwc: %s has %d elements, expected %d" % (nm, t.numel(), c))
+    ws, ws_bytes = _roi_epilogue_and_plan("roi_align_nhwc", lib, feat, r, pooled, c, scale, shift)
     if out is None:
         out = torch.empty((r, pooled, pooled, c), dtype=torch.float32, device=feat.device)
-    ws_bytes = lib.frcnn_roi_align_fwd_ws_bytes(h, w, c, r, pooled)
-    ws = _workspace(ws_bytes, feat.device) if ws_bytes else None
-    if scale is not None or shift is not None or relu:
-        _hip.check(lib.frcnn_roi_align_fwd_affine(_ptr(feat), n, h, w, c, _ptr(rois), _ptr(roi_count), r, int(rois_per_image),
-                                                  pooled, float(spatial_scale), int(sampling_ratio), _ptr(level_of_roi), level,
-                                                  _ptr(out), _ptr(scale), _ptr(shift), int(bool(relu)), _ptr(ws), ws_bytes,
-                                                  _stream()), "frcnn_roi_align_fwd_affine")
-        return out
-    _hip.check(lib.frcnn_roi_align_fwd(_ptr(feat), n, h, w, c, _ptr(rois), _ptr(roi_count), r, int(rois_per_image), pooled,
-                                       float(spatial_scale), int(sampling_ratio), _ptr(level_of_roi), level, _ptr(out),
-                                       _ptr(ws), ws_bytes, _stream()), "frcnn_roi_align_fwd")
+    _hip.check(lib.frcnn_roi_align_fwd_affine(_ptr(feat), n, h, w, c, _ptr(rois), _ptr(roi_count), r, int(rois_per_image),
+                                              pooled, float(spatial_scale), int(sampling_ratio), _ptr(level_of_roi), level,
+                                              _ptr(out), _ptr(scale), _ptr(shift), int(bool(relu)), _ptr(ws), ws_bytes,
+                                              _stream()), "frcnn_roi_align_fwd_affine")
     return out
 
 
@@ -962,16 +964,10 @@ def roi_align_split(feat, rois, pooled, spatial_scale, split_c, sampling_ratio=0
     n, h, w, c = feat.shape
     if n != 1 or rois.shape[1] != 5:
         raise _hip.HipError("roi_align_split: one image, rois (R,5)")
-    for nm, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _dev_f32(t, nm)
-            if t.numel() != c:
-                raise _hip.HipError("roi_align_split: %s has %d elements, expected %d" % (nm, t.numel(), c))
     r = rois.shape[0]
+    ws, ws_bytes = _roi_epilogue_and_plan("roi_align_split", lib, feat, r, pooled, 4, scale, shift)   # one descriptor per piece
     out1 = torch.empty((r, pooled, pooled, split_c), dtype=torch.float32, device=feat.device)
     out2 = torch.empty((r, pooled, pooled, c - split_c), dtype=torch.float32, device=feat.device)
-    ws_bytes = lib.frcnn_roi_align_fwd_ws_bytes(h, w, 4, r, pooled)
-    ws = _workspace(ws_bytes, feat.device)
     _hip.check(lib.frcnn_roi_align_fwd_split(_ptr(feat), h, w, c, _ptr(rois), _ptr(roi_count), r, pooled, float(spatial_scale),
                                              int(sampling_ratio), int(split_c), _ptr(out1), _ptr(out2), _ptr(scale), _ptr(shift),
                                              int(bool(relu1)), int(bool(relu2)), _ptr(ws), ws_bytes, _stream()),
