@@ -30,6 +30,9 @@ SOURCES = {
     "dwconv_bwd.hip": ["-ffp-contract=off"],
     "conv_wgrad.hip": [],
     "boxes.hip": ["-ffp-contract=off"],
+    "topk.hip": ["-ffp-contract=off"],
+    "nms.hip": ["-ffp-contract=off"],
+    "class_filter.hip": ["-ffp-contract=off"],
     "roi_align.hip": ["-ffp-contract=off"],
     "head.hip": ["-ffp-contract=off"],
     "train_ops.hip": ["-ffp-contract=off"],

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "common.h"
 
 namespace frcnn {
 
@@ -54,11 +55,14 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v 
 __device__ __forceinline__ float clamp_minf(float v, float lo) { return v < lo ? lo : v; }
 __device__ __forceinline__ float clamp_maxf(float v, float hi) { return v > hi ? hi : v; }
 
-// What happens when IoU == threshold exactly is a RUN-TIME choice (frcnn_nms_set_suppress_at_equal, csrc/boxes.hip; DESIGN.md
+// What happens when IoU == threshold exactly is a RUN-TIME choice (frcnn_nms_set_suppress_at_equal, csrc/nms.hip; DESIGN.md
 // section 1): torchvision 0.4.0 (req.txt:283, not vendored) suppresses on `iou >= threshold` in its CPU kernel and on
 // `iou > threshold` in its CUDA kernel.  The default follows the CPU kernel - the path the reference is compared against.
 // The kernels below always test `iou > t`; for the inclusive form the entry points hand them t = nextafterf(threshold, -inf):
 // no float lies strictly between the two, so `iou > t` IS `iou >= threshold`, bit for bit, NaN included (both false).
+inline float nms_kernel_thresh(float thresh) {
+  return frcnn_nms_get_suppress_at_equal() ? nextafterf(thresh, -INFINITY) : thresh;
+}
 
 // IoU test of torchvision.ops.nms: areas (x2-x1)*(y2-y1) without +1, suppress when iou > thresh (see above).
 __device__ __forceinline__ bool iou_gt(const float* a, const float* b, float thresh) {
@@ -129,91 +133,6 @@ __device__ __forceinline__ void block_bitonic_sort(uint64_t* keys, int npad) {
       __syncthreads();
     }
   }
-}
-
-// Greedy scan over a precomputed suppression bit-matrix by ONE wave (lane = threadIdx.x & 63).
-// mask[i*nb + w] bit b set  <=>  box (w*64+b) has IoU > thresh with box i and (w*64+b) > i.
-// Boxes are in descending-score order.  Writes survivors' positions to keep_idx (first max_keep of them)
-// and optional per-box bytes to keep_mask (pre-zeroed by the caller).  nb <= 256.
-// MaskPtr: `const uint64_t*` (global) or an address_space(3) pointer when the matrix lives in LDS - a generic pointer
-// would turn every row fetch into a flat load (40 of the 75 us of the per-class filter kernel were that).
-template <typename MaskPtr, typename KeepPtr>
-__device__ __forceinline__ int wave_nms_scan(MaskPtr mask, int nb, int n, int max_keep, KeepPtr keep_idx,
-                                             uint8_t* keep_mask) {
-  const int lane = threadIdx.x & 63;
-  uint64_t rm0 = 0, rm1 = 0, rm2 = 0, rm3 = 0;  // removed bits of words lane, lane+64, lane+128, lane+192
-  int count = 0;
-  // The chain per 64-box chunk is: diagonal word of the 64 rows -> in-register greedy resolve -> rows of the kept boxes
-  // OR-ed into the removed set -> next chunk.  Two memory latencies per chunk would sit on that chain; the diagonal
-  // word of the NEXT chunk does not depend on anything computed here, so it is fetched one chunk ahead, and the rows
-  // of up to four kept boxes are requested together before any of them is consumed.
-  uint64_t d_next = (lane < n) ? mask[(size_t)lane * nb] : 0ull;
-  for (int c = 0; c < nb && c * 64 < n && count < max_keep; ++c) {
-    const int i = c * 64 + lane;
-    const uint64_t d = d_next;
-    {
-      const int in = i + 64;
-      d_next = (c + 1 < nb && in < n) ? mask[(size_t)in * nb + (c + 1)] : 0ull;
-    }
-    const int slot = c >> 6;
-    const uint64_t mine = slot == 0 ? rm0 : slot == 1 ? rm1 : slot == 2 ? rm2 : rm3;
-    const uint64_t rw = readlane_u64(mine, c & 63);
-    const int live = n - c * 64;
-    const uint64_t valid = live >= 64 ? ~0ull : ((1ull << live) - 1ull);
-    uint64_t alive = ~rw & valid;
-    uint64_t kept = 0;
-    int nk = 0;
-    while (alive != 0 && count + nk < max_keep) {
-      const int b = __builtin_ctzll(alive);
-      kept |= 1ull << b;
-      ++nk;
-      const uint64_t db = readlane_u64(d, b);
-      alive &= ~(db | (1ull << b));
-    }
-    if ((kept >> lane) & 1ull) {
-      const int pos = count + __builtin_popcountll(kept & ((1ull << lane) - 1ull));
-      keep_idx[pos] = i;
-      if (keep_mask) keep_mask[i] = 1;
-    }
-    count += nk;
-    if (count >= max_keep) break;
-    uint64_t todo = kept;
-    while (todo != 0) {
-      MaskPtr rows[4];
-      int nr = 0;
-      for (; nr < 4 && todo != 0; ++nr) {
-        rows[nr] = mask + (size_t)(c * 64 + __builtin_ctzll(todo)) * nb;
-        todo &= todo - 1ull;
-      }
-      for (int q = nr; q < 4; ++q) rows[q] = rows[0];      // duplicates: OR is idempotent
-      // unconditional loads at a clamped word index (issued back to back), masked afterwards; slots beyond the row
-      // length are skipped by a wave-uniform branch
-      uint64_t v[4][4];
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) {
-        if (s4 * 64 < nb) {
-          const int w = lane + 64 * s4;
-          const int wc = min(w, nb - 1);
-          const bool ok = w > c && w < nb;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q][s4] = rows[q][wc];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q][s4] = ok ? v[q][s4] : 0ull;
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q][s4] = 0ull;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        rm0 |= v[q][0];
-        rm1 |= v[q][1];
-        rm2 |= v[q][2];
-        rm3 |= v[q][3];
-      }
-    }
-  }
-  return count;
 }
 
 }  // namespace frcnn

@@ -1,6 +1,7 @@
 // Shared host-side helpers of libfrcnn_hip.so (gfx950 only; no other backend is compiled in).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
@@ -19,6 +20,24 @@ inline int check_launch(const char* what) {
 }
 
 __host__ __device__ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline int next_pow2(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+// Raise Kernel's dynamic-LDS limit to `bytes`, once per high-water mark (the attribute call is idempotent: a race only
+// repeats it).  `who` names the entry point in the error text.
+template <auto Kernel>
+int ensure_dynamic_lds(size_t bytes, const char* who) {
+  static std::atomic<size_t> high_water{0};
+  if (bytes <= high_water.load()) return FRCNN_OK;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)bytes);
+  if (e != hipSuccess) return fail(FRCNN_ERR_LAUNCH, "%s: set LDS size: %s", who, hipGetErrorString(e));
+  high_water.store(bytes);
+  return FRCNN_OK;
+}
 
 // Device memory initialisation / copies inside the library's launch sequences, as KERNEL launches (default) instead of
 // hipMemsetAsync / hipMemcpyAsync: a stream capture then holds kernel nodes only.  ROCm 7's packet-captured replay of a

@@ -664,26 +664,16 @@ inline bool unit_conv(const WgradParams& p) { return p.R == 1 && p.S == 1 && p.s
 template <int TI, bool UNIT>
 int launch_dma(const WgradParams& p, dim3 grid, hipStream_t stream) {
   constexpr size_t lds = (size_t)WG_LDS_FLOATS * sizeof(float);
-  static std::atomic<bool> configured{false};   // idempotent attribute call: a race only repeats it
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_f32<TI, UNIT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv_wgrad_dma_f32: set LDS size: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  const int rc = frcnn::ensure_dynamic_lds<&conv_wgrad_dma_f32<TI, UNIT>>(lds, "conv_wgrad_dma_f32");
+  if (rc != FRCNN_OK) return rc;
   hipLaunchKernelGGL((conv_wgrad_dma_f32<TI, UNIT>), grid, dim3(256), lds, stream, p);
   return frcnn::check_launch("conv_wgrad_dma_f32");
 }
 template <int TI, bool UNIT>
 int launch_dma_grouped(const WgradParams& p, dim3 grid, const WgradGroups& g, const WgradOuts& o, hipStream_t stream) {
   constexpr size_t lds = (size_t)WG_LDS_FLOATS * sizeof(float);
-  static std::atomic<bool> configured{false};
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_grouped_f32<TI, UNIT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "conv_wgrad_dma_grouped_f32: set LDS size: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  const int rc = frcnn::ensure_dynamic_lds<&conv_wgrad_dma_grouped_f32<TI, UNIT>>(lds, "conv_wgrad_dma_grouped_f32");
+  if (rc != FRCNN_OK) return rc;
   hipLaunchKernelGGL((conv_wgrad_dma_grouped_f32<TI, UNIT>), grid, dim3(256), lds, stream, p, g, o);
   return frcnn::check_launch("conv_wgrad_dma_grouped_f32");
 }

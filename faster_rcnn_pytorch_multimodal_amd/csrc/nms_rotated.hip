@@ -1,6 +1,6 @@
 // Rotated BEV NMS: greedy suppression of yawed 7-DoF boxes [xc,yc,zc,l,w,h,ry] on their ROTATED footprints - the form the
 // reference's authors left commented out at lib/utils/filter_predictions.py:56-57 ("Turned off auto rotating"); the
-// shipped rule (:55-67) suppresses on the yaw-less rectangle xc -+ l/2, yc -+ w/2 (boxes.hip filter_class_*_kernel<7>).
+// shipped rule (:55-67) suppresses on the yaw-less rectangle xc -+ l/2, yc -+ w/2 (class_filter.hip, E = 7).
 // Opt-in (cfg.TEST.NMS_ROTATED), no default changes.
 //
 // Contract (utils/bbox.nms_rotated_host is its host statement).  Boxes in (score descending, RoI index ascending) order,
@@ -15,30 +15,28 @@
 // or an infinity anywhere makes it false and the pair takes the full computation.
 //
 // Three launches on the caller's stream, sized by the worst case (n_cap boxes), the live counts read on the device; no
-// host synchronisation, no memset / memcpy nodes:
-//   1. stage   one workgroup per class: threshold, rank-sort the (score, RoI) keys like filter_class_small_kernel, write
-//              the sorted keys and one staged box (box_geom<EVAL_TYPE_BEV>: corners, edge vectors, area; plus the
-//              bounding circle) per box to the workspace.  Stand-alone entry: the boxes arrive sorted, one thread per box.
+// host synchronisation, no memset / memcpy nodes.  The steps that do not depend on the overlap (select, rank, fixed
+// point, positions, cut, write) are those of class_filter.h, shared with the axis-aligned filters.
+//   1. stage   one workgroup per class: select_class_keys, rank_sort_keys; write the sorted keys and one staged box
+//              (box_geom<EVAL_TYPE_BEV>: corners, edge vectors, area; plus the bounding circle) per box to the
+//              workspace.  Stand-alone entry: the boxes arrive sorted, one thread per box.
 //   2. pair    grid = classes x 64x64 word tiles (w >= c) of the upper triangle x the 64 boxes j of word w.  One wave:
 //              lane = predecessor i of word c, its staged box in registers, box j read as a broadcast, ONE overlap per
 //              lane.  Each lane owns two Poly slots as LDS columns (2 x 8 vertices x 2 doubles x 64 lanes = 16 KiB, like
 //              frcnn_eval_match_kernel with a quarter of its lanes: up to 10 workgroups per compute unit).  The wave's
 //              ballot over its 64 verdicts is the predecessor word P[j][c], stored whole: every word the decide step
 //              reads is written exactly once, so P needs no clearing and no atomics.  A clip is a chain of dependent
-//              float64 operations, so the phase lasts as long as the clips ONE lane does in turn: one,
-//              chosen by measurement against 2, 4 and 8 boxes j per wave (profiles/rotated_nms.md).  300 RoIs are 960
-//              waves per class, 1024 RoIs 8704.
-//   3. decide  one workgroup per class: the predecessor-matrix fixed point of filter_class_small_kernel
-//              ( keep(j) <=> no kept predecessor in P[j] ), then the max_dets cut with ties (lib/model/test.py:213-221)
-//              and the outputs.  Up to 1024 boxes P sits in LDS (1024 x 16 words = 128 KiB of gfx950's 160 KiB); the
-//              stand-alone entry beyond that reads it from the workspace (L2).
+//              float64 operations, so the phase lasts as long as the clips ONE lane does in turn: one, chosen by
+//              measurement against 2, 4 and 8 boxes j per wave (profiles/rotated_nms.md).  300 RoIs are 960 waves per
+//              class, 1024 RoIs 8704.
+//   3. decide  one workgroup per class: nms_fixed_point ( keep(j) <=> no kept predecessor in P[j] ), kept_positions,
+//              cut_at_max_dets (lib/model/test.py:213-221) and write_class_dets.  Up to 1024 boxes P sits in LDS (1024 x
+//              16 words = 128 KiB of gfx950's 160 KiB); the stand-alone entry beyond that reads it from the workspace.
 // Plain HIP, vector stores only.
-#include "box_math.h"
-#include "common.h"
+#include "class_filter.h"
 #include "eval_overlap.h"
 
 #include <algorithm>
-#include <atomic>
 
 using namespace frcnn;
 using namespace frcnn_eval;
@@ -109,22 +107,11 @@ __global__ __launch_bounds__(ROT_THREADS) void rot_stage_filter_kernel(const flo
   double* geom = reinterpret_cast<double*>(my + l.geom);
   uint64_t* keys = reinterpret_cast<uint64_t*>(my + l.keys);
   const int R = roi_count ? max(0, min(*roi_count, num_rois)) : num_rois;
-  if (t == 0) s_n = 0;
-  __syncthreads();
-  for (int r = t; r < R; r += ROT_THREADS) {
-    const float sc = cls_prob[(size_t)r * num_classes + cls];
-    if (sc > thresh) raw[atomicAdd(&s_n, 1)] = ((uint64_t)desc_key(sc) << 32) | (uint32_t)r;
-  }
-  __syncthreads();
-  const int n = s_n;
-  for (int i = t; i < n; i += ROT_THREADS) {
-    const uint64_t mine = raw[i];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) rank += raw[j] < mine ? 1 : 0;
-    keys[rank] = mine;
-    const uint32_t r = (uint32_t)(mine & 0xFFFFFFFFu);
-    stage_box(pred_boxes + ((size_t)r * num_classes + cls) * 7, geom, num_rois, rank);
-  }
+  const int n = select_class_keys<ROT_THREADS>(cls_prob, R, num_classes, cls, thresh, raw, &s_n);
+  rank_sort_keys<ROT_THREADS>(raw, n, [&](int rank, uint64_t key) {
+    keys[rank] = key;
+    stage_box(pred_boxes + ((size_t)(uint32_t)(key & 0xFFFFFFFFu) * num_classes + cls) * 7, geom, num_rois, rank);
+  });
   if (t == 0) *reinterpret_cast<int*>(my + l.count) = n;
 }
 
@@ -198,65 +185,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void rot_pair_kernel(unsigned char* _
 }
 
 // ---- 3. decide and write ------------------------------------------------------------------------------------------------
-// Greedy NMS as the unique fixed point of  keep(j) <=> no kept predecessor in P[j]  (see filter_class_small_kernel): in
-// every round an undecided box with a kept predecessor is removed, one whose predecessors are all removed is kept; both
-// verdicts are final when made, so the sets may be read while other threads add to them.  Called by the whole workgroup;
-// leaves the kept set in kept_set[0 .. nbl) and returns nothing before a barrier.
-__device__ inline void rot_fixed_point(const uint64_t* P, int stride, int n, unsigned long long* kept_set,
-                                       unsigned long long* rem_set) {
-  const int t = threadIdx.x;
-  for (int e = t; e < 2 * (ROT_NMS_MAX / 64); e += ROT_THREADS) kept_set[e] = 0ull;   // rem_set follows kept_set
-  unsigned undecided = 0u;
-#pragma unroll
-  for (int q = 0; q < ROT_PER; ++q) undecided |= (t + q * ROT_THREADS < n) ? 1u << q : 0u;
-  for (;;) {
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < ROT_PER; ++q) {
-      if (!(undecided & (1u << q))) continue;
-      const int j = t + q * ROT_THREADS;
-      bool any_kept = false, all_removed = true;
-      for (int w = 0; w <= (j >> 6); ++w) {                 // predecessors of box j live in words 0 .. j / 64
-        uint64_t pre = P[(size_t)j * stride + w];
-        if (w == (j >> 6)) pre &= (1ull << (j & 63)) - 1ull;
-        any_kept |= (pre & kept_set[w]) != 0ull;
-        all_removed &= (pre & ~rem_set[w]) == 0ull;
-      }
-      if (any_kept) {
-        atomicOr(&rem_set[j >> 6], 1ull << (j & 63));
-        undecided &= ~(1u << q);
-      } else if (all_removed) {
-        atomicOr(&kept_set[j >> 6], 1ull << (j & 63));
-        undecided &= ~(1u << q);
-      }
-    }
-    if (__syncthreads_count(undecided != 0u ? 1 : 0) == 0) break;
-  }
-}
-
-// position of every kept box among the kept ones (ascending box order) -> order[pos] = box; returns the kept count
-__device__ inline int rot_positions(const unsigned long long* kept_set, int n, int* order) {
-  const int t = threadIdx.x, nbl = (n + 63) / 64;
-  int total = 0;
-#pragma unroll
-  for (int q = 0; q < ROT_PER; ++q) {
-    const int j = t + q * ROT_THREADS;
-    int before = 0;
-    total = 0;
-    uint64_t mine = 0ull;
-    for (int w = 0; w < nbl; ++w) {
-      const uint64_t kw = kept_set[w];
-      const int pc = __builtin_popcountll(kw);
-      if (w < (j >> 6)) before += pc;
-      if (w == (j >> 6)) mine = kw;
-      total += pc;
-    }
-    if (j < n && ((mine >> (j & 63)) & 1ull)) order[before + __builtin_popcountll(mine & ((1ull << (j & 63)) - 1ull))] = j;
-  }
-  __syncthreads();
-  return total;
-}
-
+// The fixed point over P, the kept boxes' positions, the cut and the outputs: class_filter.h, ROT_PER boxes per thread.
 // Filter: one workgroup per class; class 0 (background) writes its empty slice of every output.
 __global__ __launch_bounds__(ROT_THREADS) void rot_decide_filter_kernel(
     const float* __restrict__ pred_boxes, const float* __restrict__ cls_prob, int num_rois, int num_classes, int max_dets,
@@ -266,13 +195,7 @@ __global__ __launch_bounds__(ROT_THREADS) void rot_decide_filter_kernel(
   __shared__ unsigned long long s_sets[2 * (ROT_NMS_MAX / 64)];
   constexpr int E = 7;
   const int cls = blockIdx.x, t = threadIdx.x;
-  if (cls == 0) {
-    for (int e = t; e < max_out * (E + 1); e += ROT_THREADS) dets[e] = 0.f;
-    if (det_roi)
-      for (int e = t; e < max_out; e += ROT_THREADS) det_roi[e] = -1;
-    if (t == 0) det_count[0] = 0;
-    return;
-  }
+  if (cls == 0) return fill_background<E, ROT_THREADS>(max_out, dets, det_count, det_roi);
   const RotLayout l = rot_layout(num_rois);
   const unsigned char* my = ws + (size_t)(cls - 1) * ws_per_class;
   const uint64_t* __restrict__ Pg = reinterpret_cast<const uint64_t*>(my + l.pred);
@@ -285,34 +208,11 @@ __global__ __launch_bounds__(ROT_THREADS) void rot_decide_filter_kernel(
     const int j = e / nbl, w = e - j * nbl;
     if (w <= (j >> 6)) P[e] = Pg[(size_t)j * l.nbl + w];
   }
-  rot_fixed_point(P, nbl, n, s_sets, s_sets + ROT_NMS_MAX / 64);
-  int kept = rot_positions(s_sets, n, order);
-  // test.py:213-221: if more than max_dets survive keep score >= the max_dets-th best (ties stay).  Keys ascend along
-  // `order`, so the survivors of the cut are a prefix
-  if (max_dets > 0 && kept > max_dets) {
-    const uint32_t cut = (uint32_t)(keys[order[max_dets - 1]] >> 32);     // ascending key = descending score
-    int ties = 0;
-    for (int base = max_dets; base < kept; base += ROT_THREADS) {
-      const int m = base + t;
-      ties += __syncthreads_count(m < kept && (uint32_t)(keys[order[m]] >> 32) <= cut);
-    }
-    kept = max_dets + ties;
-  }
-  kept = min(kept, max_out);
-  float* out = dets + (size_t)cls * max_out * (E + 1);
-  for (int e = t; e < max_out * (E + 1); e += ROT_THREADS) {
-    const int i = e / (E + 1), q = e - i * (E + 1);
-    float v = 0.f;
-    int roi = -1;
-    if (i < kept) {
-      const uint32_t r = (uint32_t)(keys[order[i]] & 0xFFFFFFFFu);
-      v = q < E ? pred_boxes[((size_t)r * num_classes + cls) * E + q] : cls_prob[(size_t)r * num_classes + cls];
-      roi = (int)r;
-    }
-    out[e] = v;
-    if (det_roi && q == 0) det_roi[(size_t)cls * max_out + i] = roi;
-  }
-  if (t == 0) det_count[cls] = kept;
+  nms_fixed_point<ROT_THREADS, ROT_PER>(P, nbl, n, s_sets, s_sets + ROT_NMS_MAX / 64);
+  int kept = kept_positions<ROT_THREADS, ROT_PER>(s_sets, n, order);
+  kept = cut_at_max_dets<ROT_THREADS>(keys, order, kept, max_dets, reinterpret_cast<int*>(s_sets + ROT_NMS_MAX / 64));
+  write_class_dets<E, ROT_THREADS>(pred_boxes, cls_prob, num_classes, cls, keys, order, kept, max_out, dets, det_count,
+                                   det_roi);
 }
 
 // Stand-alone: the outputs of frcnn_nms.  P is read from the workspace (up to 4096 boxes x 64 words).
@@ -325,8 +225,9 @@ __global__ __launch_bounds__(ROT_THREADS) void rot_decide_sorted_kernel(const un
   const RotLayout l = rot_layout(n_max);
   const int n = *reinterpret_cast<const int*>(ws + l.count);
   const int t = threadIdx.x;
-  rot_fixed_point(reinterpret_cast<const uint64_t*>(ws + l.pred), l.nbl, n, s_sets, s_sets + ROT_NMS_MAX / 64);
-  const int kept = min(rot_positions(s_sets, n, order), max_keep);
+  nms_fixed_point<ROT_THREADS, ROT_PER>(reinterpret_cast<const uint64_t*>(ws + l.pred), l.nbl, n, s_sets,
+                                        s_sets + ROT_NMS_MAX / 64);
+  const int kept = min(kept_positions<ROT_THREADS, ROT_PER>(s_sets, n, order), max_keep);
   for (int i = t; i < max_keep; i += ROT_THREADS) keep_idx[i] = i < kept ? (int64_t)order[i] : 0;
   if (keep_mask) {
     for (int j = t; j < n_max; j += ROT_THREADS) keep_mask[j] = 0;
@@ -403,13 +304,8 @@ extern "C" int frcnn_filter_per_class_lidar_rot(const float* pred_boxes, const f
   rc = rot_launch_pairs(ws, per_class, num_rois, num_classes - 1, nms_thresh, stream);
   if (rc != FRCNN_OK) return rc;
   const size_t lds = rot_decide_lds(num_rois);
-  static std::atomic<size_t> configured{0};
-  if (lds > configured.load()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rot_decide_filter_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(FRCNN_ERR_LAUNCH, "filter_per_class_lidar_rot: set LDS size: %s", hipGetErrorString(e));
-    configured.store(lds);
-  }
+  rc = ensure_dynamic_lds<&rot_decide_filter_kernel>(lds, "filter_per_class_lidar_rot");
+  if (rc != FRCNN_OK) return rc;
   hipLaunchKernelGGL(rot_decide_filter_kernel, dim3(num_classes), dim3(ROT_THREADS), lds, stream, pred_boxes, cls_prob,
                      num_rois, num_classes, max_dets, max_out, dets, det_count, det_roi, (const unsigned char*)w, per_class);
   return check_launch("rot_decide_filter_kernel");

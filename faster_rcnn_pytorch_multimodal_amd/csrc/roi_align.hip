@@ -1033,13 +1033,8 @@ extern "C" int frcnn_roi_align_fwd_affine(const float* feat, int n, int h, int w
                        "h*w*64 B of LDS (got %dx%dx%d)", h, w, c);
   if ((g_roi_variant == 5 || (g_roi_variant == 0 && RES_AUTO && !has_epi)) && resident_ok(h, w, c, pooled)) {
     const size_t lds = res_lds_bytes(h, w);
-    static std::atomic<size_t> configured{0};
-    if (lds > configured.load()) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&roi_align_fwd_resident),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return frcnn::fail(FRCNN_ERR_LAUNCH, "roi_align_fwd: set LDS size: %s", hipGetErrorString(e));
-      configured.store(lds);
-    }
+    const int rc = frcnn::ensure_dynamic_lds<&roi_align_fwd_resident>(lds, "roi_align_fwd");
+    if (rc != FRCNN_OK) return rc;
     const int nslices = c / 16;
     // one workgroup per CU in total: RoI groups share a channel slice (each reloads the map slice from L2)
     const int per_image_rois = rois_per_image > 0 ? rois_per_image : num_rois;

@@ -343,11 +343,6 @@ __global__ __launch_bounds__(PTL_THREADS) void ptl_kernel(const float* __restric
   }
 }
 
-int next_pow2(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
 unsigned grid_for(size_t items, unsigned cap = 4096) { return (unsigned)std::min<size_t>((items + 255) / 256, cap); }
 
 struct AtlLayout {
@@ -509,13 +504,8 @@ int launch_ptl(const float* rois, const float* roi_scores, const int* roi_count,
   for (int q = 0; q < 7; ++q) { norm.means[q] = q < E ? means_host[q] : 0.f; norm.stds[q] = q < E ? stds_host[q] : 1.f; }
   const int npad = next_pow2(std::max(num_rois, 2));
   const size_t lds = (size_t)npad * 16 + (size_t)num_rois * 4;
-  static std::atomic<size_t> configured{0};
-  if (lds > configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ptl_kernel<E>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(FRCNN_ERR_LAUNCH, "proposal_target_layer: set LDS size: %s", hipGetErrorString(e));
-    configured = lds;
-  }
+  const int lds_rc = ensure_dynamic_lds<&ptl_kernel<E>>(lds, "proposal_target_layer");
+  if (lds_rc != FRCNN_OK) return lds_rc;
   const int fg_quota = (int)lrintf(fg_fraction * (float)rois_per_frame);   // int(round(...)) (:44-45)
   hipLaunchKernelGGL(ptl_kernel<E>, dim3(1), dim3(PTL_THREADS), lds, static_cast<hipStream_t>(stream_), rois, roi_scores,
                      roi_count, num_rois, skip, anchors3d, true_gt, out_anchors3d, gt_boxes, num_gt, num_gt_dev, num_classes,

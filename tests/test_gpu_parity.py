@@ -5,6 +5,7 @@ The loss, Monte-Carlo statistics and small training kernels are taken to their e
 Bars: bit-exact for indices, orders and keep masks; <= 1e-4 abs on box / score tensors; feature tensors
 (unbounded magnitude) within 2e-5 of the tensor's max magnitude (fp32 accumulation-order noise).
 """
+import functools
 import os
 
 import numpy as np
@@ -846,6 +847,103 @@ def test_filter_per_class_matches_oracle(hip, thresh, max_dets, r, variant, nms_
             np.testing.assert_array_equal(got, want)
     assert counts[0] == 0
     hip.frcnn_filter_set_variant(0)
+
+
+_LIVE_R, _LIVE_K = 130, 3                  # three 64-box words: predecessors span word boundaries
+# isolated boxes that outrank every clustered one: two distinct scores, then a run of ties.  Six of the ties lie below
+# row 65 and three above, so the max_dets = 5 position falls inside the run for 65 live rows and for 130
+_LIVE_TOP, _LIVE_TIED = (3, 40), (10, 20, 30, 50, 63, 64, 70, 100, 129)
+
+
+@functools.lru_cache(maxsize=None)
+def _live_count_case(e, live):
+    """Inputs of test_filter_per_class_live_count_and_det_roi and the oracle's rows for the first `live` RoIs (read-only)."""
+    r, k = _LIVE_R, _LIVE_K
+    g = torch.Generator().manual_seed(4100 + e)
+    prob = F.softmax(torch.randn(r, k, generator=g) * 2, 1) * 0.85          # every clustered score < 0.85
+    special = _LIVE_TOP + _LIVE_TIED
+    for j in range(1, k):
+        prob[list(_LIVE_TOP), j] = torch.tensor([0.99, 0.98])
+        prob[list(_LIVE_TIED), j] = 0.9
+    if e == 4:
+        centres = _rand_boxes(12, g)
+        boxes = torch.cat([centres[torch.randint(0, 12, (r,), generator=g)] + torch.randn(r, 4, generator=g) * 8
+                           for _ in range(k)], 1)
+        boxes[:, 0::4] -= 30                                                # some boxes leave the frame -> clamp matters
+        for m, i in enumerate(special):
+            boxes[i] = torch.tensor([50.0 + 80 * m, 560, 70.0 + 80 * m, 580]).repeat(k)
+    else:
+        boxes = torch.zeros(r, k * 7)
+        ctr = torch.rand(12, 2, generator=g) * 300
+        for j in range(k):
+            boxes[:, j * 7 + 0:j * 7 + 2] = ctr[torch.randint(0, 12, (r,), generator=g)] + torch.randn(r, 2, generator=g) * 3
+            boxes[:, j * 7 + 2] = torch.rand(r, generator=g)
+            boxes[:, j * 7 + 3:j * 7 + 6] = torch.tensor([23.6, 10.4, 1.8]) * (0.8 + 0.4 * torch.rand(r, 3, generator=g))
+            boxes[:, j * 7 + 6] = (torch.rand(r, generator=g) - 0.5) * 3.14159
+        for m, i in enumerate(special):
+            boxes[i] = torch.tensor([500.0 + 40 * m, 500, 1, 10, 10, 2, 0.1 * m]).repeat(k)
+    info = np.array([0, 1000, 0, 600, 0, 0, 1.0], np.float32)
+    rois = torch.zeros(r, 5)
+    if e == 4:
+        _, ref, _ = O.filter_and_draw_prep(rois[:live], prob[:live], boxes[:live], info, k, 0.1)
+        clamped = O.filter_and_draw_prep(rois, prob, boxes, info, k, 0.1)[2]   # the device clamps every row it is given
+    else:
+        _, ref = O.filter_and_draw_prep_lidar(rois[:live], prob[:live], boxes[:live], k, 0.1)
+        clamped = boxes
+    return prob, boxes, clamped, ref
+
+
+@pytest.mark.parametrize("max_dets", [0, 5])
+@pytest.mark.parametrize("count", [0, 65, 130, 200])
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("e", [4, 7])
+def test_filter_per_class_live_count_and_det_roi(hip, e, variant, count, max_dets):
+    """The axis-aligned filters with a live RoI count read on the device (a count over the capacity behaves as the
+    capacity) and the det_roi output, on sentinel-filled outputs: rows and counts equal the oracle's on the first
+    min(count, 130) RoIs, every kept row is the box and score of the RoI det_roi names, every other row is 0 / -1."""
+    ops = _ops()
+    r, k = _LIVE_R, _LIVE_K
+    live = min(count, r)
+    prob, boxes, clamped, ref = _live_count_case(e, live)
+    want = [O.max_dets_cut(b, max_dets) for b in ref]
+    if max_dets and live >= 65:        # the inputs do what they were built for: the cut lands inside the run of ties
+        assert all(len(ref[j]) > max_dets and len(want[j]) > max_dets for j in range(1, k))
+    prob_dev, boxes_dev = prob.contiguous().to(DEV), boxes.contiguous().to(DEV)
+    count_dev = torch.tensor([count], dtype=torch.int32, device=DEV)
+    dets = torch.full((k, r, e + 1), float("nan"), dtype=torch.float32, device=DEV)
+    det_count = torch.full((k,), -99, dtype=torch.int32, device=DEV)
+    det_roi = torch.full((k, r), 12345, dtype=torch.int32, device=DEV)
+    ws_bytes = hip.frcnn_filter_per_class_ws_bytes(r, k)
+    ws = ops._workspace(ws_bytes, DEV)
+    hip.frcnn_filter_set_variant(variant)
+    try:
+        if e == 4:
+            rc = hip.frcnn_filter_per_class(boxes_dev.data_ptr(), prob_dev.data_ptr(), count_dev.data_ptr(), r, k, 1000.0,
+                                            600.0, 1.0, 0.1, O.TEST_NMS_THRESH, max_dets, r, dets.data_ptr(),
+                                            det_count.data_ptr(), det_roi.data_ptr(), ws.data_ptr(), ws_bytes, ops._stream())
+        else:
+            rc = hip.frcnn_filter_per_class_lidar(boxes_dev.data_ptr(), prob_dev.data_ptr(), count_dev.data_ptr(), r, k, 0.1,
+                                                  O.TEST_NMS_THRESH, max_dets, r, dets.data_ptr(), det_count.data_ptr(),
+                                                  det_roi.data_ptr(), ws.data_ptr(), ws_bytes, ops._stream())
+        assert rc == 0, hip.frcnn_last_error()
+        torch.cuda.synchronize()
+    finally:
+        hip.frcnn_filter_set_variant(0)
+    assert torch.equal(boxes_dev.cpu(), clamped)
+    dets, det_count, det_roi = dets.cpu().numpy(), det_count.cpu().numpy(), det_roi.cpu().numpy()
+    clamped, prob = clamped.numpy(), prob.numpy()
+    assert det_count[0] == 0 and (det_roi[0] == -1).all() and (dets[0] == 0).all()
+    for j in range(1, k):
+        n = int(det_count[j])
+        assert n == len(want[j]), (j, n, len(want[j]))
+        if n:
+            # the oracle's cut keeps its NMS order (score descending, ties by RoI index), which is the device's order
+            np.testing.assert_array_equal(dets[j, :n], want[j][np.lexsort((np.arange(n), -want[j][:, -1]))])
+        roi = det_roi[j, :n]
+        assert ((roi >= 0) & (roi < live)).all()
+        np.testing.assert_array_equal(dets[j, :n, :e], clamped[roi, j * e:(j + 1) * e])
+        np.testing.assert_array_equal(dets[j, :n, e], prob[roi, j])
+        assert (det_roi[j, n:] == -1).all() and (dets[j, n:] == 0).all()
 
 
 def test_empty_and_degenerate_inputs(hip):
