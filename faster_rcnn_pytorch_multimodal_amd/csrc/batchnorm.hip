@@ -69,7 +69,7 @@ __device__ __forceinline__ void bn_bwd_final(double s, double q, int c, int C, c
 
 // part[g][c] = (sum_m a[m][c], sum_m b[m][c]) over the rows of group g, where
 //   forward : a = y,  b = y*y
-//   backward: a = g,  b = g * xhat     with g = relu ? (out > 0 ? dout : 0) : dout,  xhat = (y - mean) * invstd
+//   backward: a = g,  b = g * xhat     with g = relu ? (out > 0 ? dout : 0) : dout,  xhat = (y - mean) * invstd in fp64
 template <bool BWD>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ y, const float* __restrict__ dout,
                                                         const float* __restrict__ out, const float* __restrict__ mean,
@@ -87,9 +87,11 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
       if (BWD) {
         float g = dout[i];
         if (relu && !(out[i] > 0.f)) g = 0.f;
-        const float xh = (y[i] - mu) * is;
+        // xhat in fp64 here: rounded to fp32 first, the sum would carry 2^-23 sum|g xhat|, and where d_gamma cancels
+        // (|sum g xhat| << sum |g xhat|) that is many ulps of k = d_gamma / M in every element of dy
+        const double xh = ((double)y[i] - (double)mu) * (double)is;
         a += (double)g;
-        b += (double)g * (double)xh;
+        b += (double)g * xh;
       } else {
         const float v = y[i];
         a += (double)v;

@@ -694,7 +694,8 @@ int frcnn_act_bwd(const float* dy, const float* y, const float* scale, int relu,
  *   bwd: g = relu ? (out > 0 ? dout : 0) : dout; dbeta = sum g; dgamma = sum g*xhat;
  *        dy = gamma*invstd*(g - dbeta/rows - xhat*dgamma/rows); dres = g (may be NULL).
  *        accumulate != 0: dgamma / dbeta are the parameters' own gradient buffers and are added into.
- * Column sums are carried in fp64 and added in a fixed order.
+ * Column sums are carried in fp64 and added in a fixed order; the summand g*xhat of dgamma is formed in fp64 too
+ * (dy's own xhat is fp32).
  * counters: frcnn_bn_train_counters(c) ints, zero on entry and left zero, not shared by launches that can be in flight
  * together (the rule of frcnn_conv2d_bwd_weight's counters): the last workgroup of a 64-channel column block turns the column
  * sums into the statistics / coefficients itself - two launches per call instead of three.  NULL: a separate pass does. */

@@ -1,0 +1,718 @@
+"""The train-mode BatchNorm kernels (csrc/batchnorm.hip: frcnn_bn_train_fwd / frcnn_bn_train_bwd, the column-sum kernel
+with its fused last-arriver pass, the two stand-alone final passes and the two apply kernels) at their edges, called
+through ops.py, the C ABI and autograd_ops._BnTrainFn, against float64.
+
+Case builders return (inputs, float64 statistics with their bars); ``check_case`` derives every other float64 reference
+and bar from the inputs and from the saved statistics of the side under test.  The GPU tests (marked gpu) run the kernels;
+the unmarked ``test_cpu_restatement_*`` tests restate the kernels' arithmetic on the CPU - fp64 one-pass column sums in the
+kernel's row grouping (row m belongs to wave m % 4 of group (m / 4) % 64; wave sums, then ((w0 + w1) + w2) + w3, then the 64
+groups in order; the summands y, y^2, g and g xhat formed in fp64), then fp32 with separately rounded operations - and go
+through the same ``check_case``.
+``test_cpu_restatement_fp32_accumulators_miss_the_bars`` is the demonstration that a subtly wrong kernel fails: the same
+restatement with fp32 accumulators misses the save_invstd bar by orders of magnitude.
+
+Inputs.  Channel c of every tensor is of regime REGIMES[c % 8]: normal N(0,1); cancel 100 + 0.05 N(0,1) (mean^2 / var =
+4e6); const_big 1000.5 in every row; zero; tiny 1e-4 N(0,1) (var << eps); large 1e3 N(0,1); outlier zeros with a single
+1e4; pm1 alternating +1 / -1.  eps = 1e-5 (as the float the kernel receives).
+
+Which case reaches which regime (rows, C):
+  (1, 8)                           one row: M = 1 in the unbiased variance, every channel constant
+  (2, 8) (3, 4) (5, 36)            most of the 64 row groups empty; M / (M - 1) large; C = 4: one f32x4 per row
+  (255, 64) (256, 68) (257, 132)   around one full pass of the 4 x 64 row stride; a second / third, ragged column block
+  (513, 8)                         third trip of the row loop
+  (8800, 128)                      layer-sized
+  (777, 2048)                      32 column blocks, 32 counters
+  (233100, 36)                     rows * C / 4 = 2097900 > 8192 * 256 with C / 4 = 9 not dividing the stride: second trip
+                                   of both apply kernels (34 MB per tensor; run once, ReLU + residual)
+  var < 0 clamp, zero variance     const_big / zero / (rows = 1) channels of every case
+  gamma / beta absent              test_absent_affine_equals_ones_and_zeros
+  momentum 0 / 0.1 / 1             test_running_statistics
+  ReLU mask at out == 0            test_relu_mask_at_zero
+  workspace reuse                  test_workspace_reuse_after_a_fuller_call
+  argument rejections              test_rejections
+  fused / stand-alone final pass   every case of test_bn_train_fwd_bwd and test_running_statistics, bit for bit
+  non-finite input in one channel  test_columns_are_independent
+  accumulating d_gamma / d_beta    test_accumulating_form
+  module level, (257, 36)          test_module_level: momentum=None (cumulative average), track_running_stats=False,
+                                   affine=False, weight or bias frozen, against a float64 nn.BatchNorm2d over three steps
+
+Bars (all derived; u = 2^-24, L = ceil(rows / 256) + 68 the longest chain of fp64 additions feeding one column).
+Statistics against a two-pass float64 mean / biased variance of the fp32 inputs:
+  save_mean     |err| <= u |mean| + L 2^-53 mean(|y|)
+  save_invstd   relative <= 4u + 0.5 varbound / (var + eps),  varbound = 2 L 2^-53 (mean^2 + var)
+Everything else as a function of the saved statistics of the side under test (outputs of one call, inputs of the next), so
+the rounding of the mean is not charged twice:
+  out           <= 4u (|(y - mean) alpha| + |beta| + |residual|)
+  d_beta        <= u |d_beta| + L 2^-53 sum |g|                      (one rounding of an fp64 sum)
+  d_gamma       <= u |d_gamma| + 4u sum |g xhat|                     (xhat formed in fp32 with two roundings)
+  dy            <= 16u |a| (|g| + |b| + |xhat k|)                    (dy = a ((g - b) - xhat k))
+  dres          the masked dout, bit for bit
+  running_mean  the fp32 restatement (1 - m) old + m save_mean, bit for bit
+  running_var   <= 2u (|(1 - m) old| + |m unb|) + m (u unb + varbound M / (M - 1)),  unb the unbiased variance
+
+Headroom of the restatement.  Every bar is a worst-case bound, not a measurement.  Its multiples of u count correctly
+rounded fp32 operations: the correctly rounded float64 result itself comes within 0.99 of u |x| over a few thousand
+channels, so nothing computed in fp32 can keep a factor below those terms, and the restatement reaches 0.99 of the
+save_mean and d_beta bars.  HEADROOM = 4 therefore divides the terms an accumulator can spoil - the ones in L 2^-53 and
+varbound, which a wrong accumulator, order or formula exceeds by orders of magnitude - and the restatement is held to
+   rounding terms + accumulation terms / 4,
+the device to the bars as written.  WIDENED lists a bar the restatement could not meet in that form, with the measured
+error; it is empty.
+
+d_gamma.  The column-sum kernel forms xhat in fp64 for the sum of g xhat.  With xhat rounded to fp32 first (two
+roundings) the restatement met the d_gamma bar, but k = d_gamma / M inherited 2^-23 sum |g xhat| / M, and where d_gamma
+cancels that is many ulps of k: dy at masked elements (g = 0) missed its bar by 2.07x in 777x2048-relu (``large``
+channels).  The d_gamma bar stays as derived for the fp32 xhat; it now has that much more room.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+DEV = "cuda:0"
+U = 2.0 ** -24                        # half an ulp, relative: the bound of one correct fp32 rounding
+E53 = 2.0 ** -53
+EPS = 1e-5
+EPS32 = float(np.float32(EPS))        # the value the kernel receives
+MOM = 0.1
+HEADROOM = 4.0
+GRID_CAP = 8192 * 256
+REGIMES = ["normal", "cancel", "const_big", "zero", "tiny", "large", "outlier", "pm1"]
+SHAPES = [(1, 8), (2, 8), (3, 4), (5, 36), (255, 64), (256, 68), (257, 132), (513, 8), (8800, 128), (777, 2048)]
+MODES = ["plain", "relu", "relu_res"]
+BIG = (233100, 36)
+CASES = [(r, c, m) for (r, c) in SHAPES for m in MODES] + [BIG + ("relu_res",)]
+OUTPUTS = ("out", "mean", "invstd", "rm", "rv", "dy", "dres", "dgamma", "dbeta")
+
+# (case id, tensor) -> (bar, error of the CPU restatement that made the derived bar too tight)
+WIDENED = {}
+
+
+def _case_id(case):
+    return "%dx%d-%s" % case
+
+
+def _ops():
+    from faster_rcnn_pytorch_multimodal_amd import ops
+    return ops
+
+
+def _hip_error():
+    from faster_rcnn_pytorch_multimodal_amd import _hip
+    return _hip.HipError
+
+
+def _bits_equal(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _chain(rows):
+    return -(-rows // 256) + 68
+
+
+def _check(case, name, got, ref, bar, side, headroom=1.0, accum=0.0):
+    """Elementwise |got - ref| <= bar; with headroom, <= bar - accum + accum / headroom, ``accum`` being the accumulation
+    terms inside ``bar`` (module docstring).  Prints the worst ratio to the bar before asserting."""
+    bar = WIDENED.get((case, name), (bar,))[0]
+    got = torch.as_tensor(got).detach().double().cpu().reshape(-1)
+    ref = torch.as_tensor(ref).detach().double().reshape(-1)
+    assert got.shape == ref.shape, (case, name, got.shape, ref.shape)
+    assert bool(torch.isfinite(ref).all()), (case, name, "reference not finite")
+    assert bool(torch.isfinite(got).all()), (case, name, "result not finite")
+    bar_t = torch.as_tensor(bar, dtype=torch.float64).reshape(-1).expand_as(ref)
+    err = (got - ref).abs()
+    safe = torch.where(bar_t > 0, bar_t, torch.ones_like(bar_t))
+    ratio_t = torch.where(err > 0, torch.where(bar_t > 0, err / safe, torch.full_like(err, float("inf"))), torch.zeros_like(err))
+    ratio = float(ratio_t.max()) if ratio_t.numel() else 0.0
+    print("BNK|%s|%s|%s|err=%.3e|ratio=%.4f" % (side, case, name, float(err.max()) if err.numel() else 0.0, ratio))
+    assert ratio <= 1.0, "%s %s (%s): worst error is %.3f of its bar (max abs %.3e)" % (case, name, side, ratio, float(err.max()))
+    if headroom > 1.0:
+        accum_t = torch.as_tensor(accum, dtype=torch.float64).reshape(-1).expand_as(ref)
+        allowed = bar_t - accum_t + accum_t / headroom
+        over = err > allowed
+        assert not bool(over.any()), "%s %s (%s): %d elements outside the bar with %gx headroom, worst %.3f of the bar" % (
+            case, name, side, int(over.sum()), headroom, ratio)
+
+
+# ================================================================================================
+# Inputs and float64 statistics
+# ================================================================================================
+def make_activation(rows, c, g):
+    n = torch.randn(rows, c, generator=g)
+    regime = torch.arange(c) % len(REGIMES)
+    y = torch.zeros(rows, c)
+    col = lambda name: regime == REGIMES.index(name)
+    y[:, col("normal")] = n[:, col("normal")]
+    y[:, col("cancel")] = 100.0 + 0.05 * n[:, col("cancel")]
+    y[:, col("const_big")] = 1000.5
+    y[:, col("tiny")] = 1e-4 * n[:, col("tiny")]
+    y[:, col("large")] = 1e3 * n[:, col("large")]
+    for ch in torch.nonzero(col("outlier")).view(-1).tolist():
+        y[(7 * ch + 3) % rows, ch] = 1e4
+    y[:, col("pm1")] = (1.0 - 2.0 * (torch.arange(rows) % 2).float()).view(rows, 1)
+    return y.contiguous()
+
+
+def constant_channels(rows, c):
+    regime = torch.arange(c) % len(REGIMES)
+    if rows == 1:
+        return torch.ones(c, dtype=torch.bool)
+    return (regime == REGIMES.index("const_big")) | (regime == REGIMES.index("zero"))
+
+
+def build_case(rows, c, mode, seed=0):
+    g = torch.Generator().manual_seed(1000 * seed + 7 * rows + c)
+    y = make_activation(rows, c, g)
+    inp = dict(y=y, gamma=torch.rand(c, generator=g) + 0.5, beta=torch.randn(c, generator=g),
+               res=torch.randn(rows, c, generator=g) if mode == "relu_res" else None, dout=torch.randn(rows, c, generator=g),
+               rm=torch.randn(c, generator=g), rv=torch.rand(c, generator=g) + 0.5, relu=mode != "plain", rows=rows, c=c)
+    return inp, statistics(y)
+
+
+@functools.lru_cache(maxsize=None)
+def bn_case(rows, c, mode):
+    return build_case(rows, c, mode)
+
+
+def statistics(y):
+    """Two-pass float64 mean / biased variance of the fp32 inputs and the statistics' bars."""
+    rows = y.shape[0]
+    y64 = y.double()
+    mean = y64.mean(0)
+    var = ((y64 - mean) ** 2).mean(0)
+    chain = _chain(rows)
+    varbound = 2 * chain * E53 * (mean ** 2 + var)
+    invstd = 1.0 / torch.sqrt(var + EPS32)
+    mean_acc, invstd_acc = chain * E53 * y64.abs().mean(0), 0.5 * varbound / (var + EPS32) * invstd
+    return dict(mean=mean, var=var, invstd=invstd, varbound=varbound, mean_acc=mean_acc, invstd_acc=invstd_acc,
+                mean_bar=U * mean.abs() + mean_acc, invstd_bar=4 * U * invstd + invstd_acc)
+
+
+def running_var_reference(stat, rows, old, momentum):
+    """float64 (1 - m) old + m unb with the kernel's own fp32 coefficients m and 1 - m, its bar and the bar's accumulation term."""
+    m32 = float(np.float32(momentum))
+    one_m = float(np.float32(1.0) - np.float32(momentum))
+    factor = rows / (rows - 1.0) if rows > 1 else 1.0
+    unb = stat["var"] * factor
+    ref = one_m * old.double() + m32 * unb
+    accum = m32 * stat["varbound"] * factor
+    return ref, 2 * U * ((one_m * old.double()).abs() + m32 * unb) + m32 * U * unb + accum, accum
+
+
+def running_mean_restated(old, momentum, save_mean):
+    m = torch.tensor(momentum, dtype=torch.float32)
+    return (torch.tensor(1.0) - m) * old + m * save_mean
+
+
+def check_case(cid, inp, stat, got, side, headroom=1.0, momentum=MOM):
+    """Every output in ``got`` (OUTPUTS, CPU tensors) against float64; see the module docstring for the bars."""
+    y, gamma, beta, res, dout, relu = (inp[k] for k in ("y", "gamma", "beta", "res", "dout", "relu"))
+    rows, c = y.shape
+    chain = _chain(rows)
+    _check(cid, "save_mean", got["mean"], stat["mean"], stat["mean_bar"], side, headroom, stat["mean_acc"])
+    _check(cid, "save_invstd", got["invstd"], stat["invstd"], stat["invstd_bar"], side, headroom, stat["invstd_acc"])
+    const = constant_channels(rows, c)
+    assert _bits_equal(got["mean"][const], y[0][const]), "a constant channel's mean is its value"
+    # apply, as a function of this side's saved statistics
+    y64, mu, istd = y.double(), got["mean"].double(), got["invstd"].double()
+    gamma64 = gamma.double() if gamma is not None else torch.ones(c, dtype=torch.float64)
+    beta64 = beta.double() if beta is not None else torch.zeros(c, dtype=torch.float64)
+    t = (y64 - mu) * (istd * gamma64)
+    pre = t + beta64 + (res.double() if res is not None else 0.0)
+    bar = 4 * U * (t.abs() + beta64.abs() + (res.double().abs() if res is not None else 0.0))
+    _check(cid, "out", got["out"], pre.clamp(min=0) if relu else pre, bar, side, headroom)
+    want = (beta if beta is not None else torch.zeros(c)).expand(rows, c)
+    if res is not None:
+        want = want + res
+    if relu:
+        want = torch.where(want > 0, want, torch.zeros(()))
+    assert _bits_equal(got["out"][:, const], want[:, const]), "a constant channel's output is beta (+ residual), bit for bit"
+    # running statistics
+    assert _bits_equal(got["rm"], running_mean_restated(inp["rm"], momentum, got["mean"]))
+    ref, bar, accum = running_var_reference(stat, rows, inp["rv"], momentum)
+    _check(cid, "running_var", got["rv"], ref, bar, side, headroom, accum)
+    # backward, as a function of this side's saved statistics and output
+    g = torch.where(got["out"] > 0, dout, torch.zeros(())) if relu else dout
+    if res is not None:
+        assert _bits_equal(got["dres"], g), "dres is the masked dout"
+    else:
+        assert got["dres"] is None
+    g64 = g.double()
+    dbeta = g64.sum(0)
+    accum = chain * E53 * g64.abs().sum(0)
+    _check(cid, "d_beta", got["dbeta"], dbeta, U * dbeta.abs() + accum, side, headroom, accum)
+    xhat = (y64 - mu) * istd
+    dgamma = (g64 * xhat).sum(0)
+    _check(cid, "d_gamma", got["dgamma"], dgamma, U * dgamma.abs() + 4 * U * (g64 * xhat).abs().sum(0), side, headroom)
+    a, b, k = gamma64 * istd, dbeta / rows, dgamma / rows
+    _check(cid, "dy", got["dy"], a * ((g64 - b) - xhat * k), 16 * U * a.abs() * (g64.abs() + b.abs() + (xhat * k).abs()),
+           side, headroom)
+
+
+# ================================================================================================
+# The kernels' arithmetic on the CPU
+# ================================================================================================
+def _column_sum(x):
+    """Sum over the rows of x (rows, C) in the kernel's grouping and order, in x's dtype."""
+    rows, c = x.shape
+    trips = -(-rows // 256)
+    x = F.pad(x, (0, 0, 0, trips * 256 - rows)).view(trips, 64, 4, c)         # row m = 256 trip + 4 group + wave
+    waves = torch.zeros(64, 4, c, dtype=x.dtype)
+    for trip in range(trips):
+        waves = waves + x[trip]
+    groups = ((waves[:, 0] + waves[:, 1]) + waves[:, 2]) + waves[:, 3]
+    total = torch.zeros(c, dtype=x.dtype)
+    for group in range(64):
+        total = total + groups[group]
+    return total
+
+
+def restate(inp, momentum=MOM, acc=torch.float64):
+    """frcnn_bn_train_fwd then frcnn_bn_train_bwd on the CPU; ``acc`` is the accumulators' type (the kernel's: float64)."""
+    y, gamma, beta, res, dout, relu = (inp[k] for k in ("y", "gamma", "beta", "res", "dout", "relu"))
+    rows, c = y.shape
+    one, zero = torch.tensor(1.0), torch.zeros(())
+    ya = y.to(acc)
+    mean = _column_sum(ya) / rows
+    var = _column_sum(ya * ya) / rows - mean * mean
+    var = torch.where(var < 0, torch.zeros((), dtype=acc), var)
+    mean_f, var_f = mean.float(), var.float()
+    invstd = one / torch.sqrt(var_f + torch.tensor(EPS, dtype=torch.float32))
+    alpha = invstd * gamma if gamma is not None else invstd * one
+    out = (y - mean_f) * alpha + (beta if beta is not None else zero)
+    if res is not None:
+        out = out + res
+    if relu:
+        out = torch.where(out > 0, out, zero)
+    m = torch.tensor(momentum, dtype=torch.float32)
+    unbiased = (var * rows / (rows - 1)).float() if rows > 1 else var_f
+    rm = (one - m) * inp["rm"] + m * mean_f
+    rv = (one - m) * inp["rv"] + m * unbiased
+    g = torch.where(out > 0, dout, zero) if relu else dout
+    xhat = (y - mean_f) * invstd
+    s, q = _column_sum(g.to(acc)), _column_sum(g.to(acc) * ((ya - mean_f.to(acc)) * invstd.to(acc)))
+    a = gamma * invstd if gamma is not None else one * invstd
+    b, k = (s / rows).float(), (q / rows).float()
+    dy = a * ((g - b) - xhat * k)
+    return dict(out=out, mean=mean_f, invstd=invstd, rm=rm, rv=rv, dy=dy, dres=g if res is not None else None,
+                dgamma=q.float(), dbeta=s.float())
+
+
+@pytest.mark.parametrize("case", CASES, ids=_case_id)
+def test_cpu_restatement_bn_train(case):
+    inp, stat = bn_case(*case) if case[:2] != BIG else build_case(*case)
+    check_case(_case_id(case), inp, stat, restate(inp), "cpu", HEADROOM)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("momentum", [0.0, 0.1, 1.0])
+def test_cpu_restatement_running_statistics(momentum, shape):
+    inp, stat = bn_case(*shape, "plain")
+    got = restate(inp, momentum)
+    check_running_statistics("%dx%d-m%g" % (shape + (momentum,)), inp, stat, got, momentum, "cpu", HEADROOM)
+
+
+@pytest.mark.parametrize("shape", [(2, 8), (5, 36), (257, 132), (8800, 128)], ids=lambda s: "%dx%d" % s)
+def test_cpu_restatement_fp32_accumulators_miss_the_bars(shape):
+    """The subtly wrong kernel: the same sums carried in fp32.  E[x^2] - E[x]^2 cancels in the ``cancel`` channels (mean 100,
+    std 0.05) at every row count, and in ``const_big`` (1000.5) at 8800 rows, and save_invstd leaves its bar by orders of
+    magnitude, while the fp64 restatement meets it with headroom (test_cpu_restatement_bn_train)."""
+    inp, stat = bn_case(*shape, "plain")
+    got = restate(inp, acc=torch.float32)
+    ratio = (got["invstd"].double() - stat["invstd"]).abs() / stat["invstd_bar"]
+    regime = torch.arange(shape[1]) % len(REGIMES)
+    cancel = ratio[regime == REGIMES.index("cancel")]
+    print("BNK|cpu-fp32-accumulators|%dx%d|save_invstd|cancel ratio min %.3e max %.3e" % (shape + (float(cancel.min()), float(cancel.max()))))
+    assert float(cancel.min()) > 100.0, "an fp32 accumulator must fail every cancel channel"
+    if shape[0] == 8800:
+        big = ratio[regime == REGIMES.index("const_big")]
+        rel = (got["invstd"].double() - stat["invstd"]).abs() / stat["invstd"]
+        print("BNK|cpu-fp32-accumulators|%dx%d|save_invstd|const_big ratio min %.3e, relative error %.3f" % (
+            shape + (float(big.min()), float(rel[regime == REGIMES.index("const_big")].max()))))
+        assert float(big.min()) > 1.0
+    with pytest.raises(AssertionError):
+        _check("%dx%d-fp32acc" % shape, "save_invstd", got["invstd"], stat["invstd"], stat["invstd_bar"], "cpu-fp32-accumulators")
+
+
+def check_running_statistics(cid, inp, stat, got, momentum, side, headroom=1.0):
+    rows, c = inp["y"].shape
+    assert _bits_equal(got["rm"], running_mean_restated(inp["rm"], momentum, got["mean"]))
+    ref, bar, accum = running_var_reference(stat, rows, inp["rv"], momentum)
+    _check(cid, "running_var", got["rv"], ref, bar, side, headroom, accum)
+    if momentum == 0.0:
+        assert _bits_equal(got["rm"], inp["rm"]) and _bits_equal(got["rv"], inp["rv"])
+    if momentum == 1.0:
+        assert _bits_equal(got["rm"], got["mean"])
+        regime = torch.arange(c) % len(REGIMES)
+        if rows == 1:
+            assert bool((got["rv"] == 0).all()), "one row: the biased variance, 0"
+        if rows == 2 and c >= 8:
+            assert bool((got["rv"][regime == REGIMES.index("pm1")] == 2.0).all()), "two rows +1 / -1: var 1, unbiased 2"
+
+
+# ================================================================================================
+# Device
+# ================================================================================================
+def _to_dev(t):
+    return None if t is None else t.to(DEV)
+
+
+def run_device(ops, inp, momentum=MOM, rm=None, rv=None, want_res=None, **grads):
+    """ops.bn_train_fwd then ops.bn_train_bwd on fresh copies; returns OUTPUTS as device tensors."""
+    y, gamma, beta, res, dout = (_to_dev(inp[k]) for k in ("y", "gamma", "beta", "res", "dout"))
+    rm = _to_dev(inp["rm"] if rm is None else rm).clone()
+    rv = _to_dev(inp["rv"] if rv is None else rv).clone()
+    out, mean, invstd = ops.bn_train_fwd(y, gamma, beta, EPS, momentum, rm, rv, res, inp["relu"])
+    dy, dres, dgamma, dbeta = ops.bn_train_bwd(dout, out, y, gamma, mean, invstd, relu=inp["relu"],
+                                               want_res=(res is not None) if want_res is None else want_res, **grads)
+    return dict(out=out, mean=mean, invstd=invstd, rm=rm, rv=rv, dy=dy, dres=dres, dgamma=dgamma, dbeta=dbeta)
+
+
+def _cpu(got):
+    return {k: (None if v is None else v.cpu()) for k, v in got.items()}
+
+
+def _same(a, b, names=OUTPUTS):
+    return [n for n in names if not _bits_equal(a[n], b[n])]
+
+
+def _counters_are_zero(ops):
+    torch.cuda.synchronize()
+    return all(int(ring.ints.abs().max()) == 0 for ring in ops._COUNTER_RINGS.values())
+
+
+def _separate_final(ops):
+    class _Ctx:
+        def __enter__(self):
+            assert ops.BN_FUSED_FINAL
+            ops.BN_FUSED_FINAL = False
+
+        def __exit__(self, *exc):
+            ops.BN_FUSED_FINAL = True
+            return False
+    return _Ctx()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=_case_id)
+def test_bn_train_fwd_bwd(hip, case):
+    ops = _ops()
+    inp, stat = bn_case(*case) if case[:2] != BIG else build_case(*case)
+    assert case[:2] != BIG or (inp["y"].numel() // 4 > GRID_CAP and GRID_CAP % (case[1] // 4) != 0)
+    fused = run_device(ops, inp)
+    with _separate_final(ops):
+        separate = run_device(ops, inp)
+    again = run_device(ops, inp)
+    assert _same(fused, separate) == [], "fused and stand-alone final pass differ"
+    assert _same(fused, again) == [], "two calls differ"
+    assert _counters_are_zero(ops)
+    check_case(_case_id(case), inp, stat, _cpu(fused), "device")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("momentum", [0.0, 0.1, 1.0])
+def test_running_statistics(hip, momentum, shape):
+    ops = _ops()
+    inp, stat = bn_case(*shape, "plain")
+    got = run_device(ops, inp, momentum)
+    check_running_statistics("%dx%d-m%g" % (shape + (momentum,)), inp, stat, _cpu(got), momentum, "device")
+    if momentum == 1.0:          # the statistic itself, whatever finite value was there before
+        other = run_device(ops, inp, momentum, rm=inp["rm"] * -3e30, rv=inp["rv"] * 1e-30)
+        assert _same(got, other, ("rm", "rv")) == []
+    with _separate_final(ops):
+        assert _same(got, run_device(ops, inp, momentum)) == []
+
+
+def _raw_call(ops, hip, inp, ws, ws_bytes, fused=True):
+    """The C ABI with a workspace of the caller's: forward, then backward, on the current stream."""
+    y, gamma, beta, res, dout = (_to_dev(inp[k]) for k in ("y", "gamma", "beta", "res", "dout"))
+    rows, c = y.shape
+    rm, rv = inp["rm"].to(DEV), inp["rv"].to(DEV)
+    out, dy, dres = torch.empty_like(y), torch.empty_like(y), torch.empty_like(y) if res is not None else None
+    mean, invstd, dgamma, dbeta = (torch.empty(c, device=DEV) for _ in range(4))
+    p, relu = ops._ptr, int(inp["relu"])
+    counters = torch.zeros(hip.frcnn_bn_train_counters(c), dtype=torch.int32, device=DEV) if fused else None
+    rc = hip.frcnn_bn_train_fwd(p(y), rows, c, p(gamma), p(beta), EPS, MOM, p(rm), p(rv), p(res), relu, p(out), p(mean), p(invstd),
+                                p(ws), ws_bytes, p(counters), ops._stream())
+    assert rc == 0, rc
+    rc = hip.frcnn_bn_train_bwd(p(dout), p(out), p(y), rows, c, p(gamma), p(mean), p(invstd), relu, p(dy), p(dres), p(dgamma),
+                                p(dbeta), 0, p(ws), ws_bytes, p(counters), ops._stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    assert counters is None or int(counters.abs().max()) == 0
+    return dict(out=out, mean=mean, invstd=invstd, rm=rm, rv=rv, dy=dy, dres=dres, dgamma=dgamma, dbeta=dbeta)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("full,sparse", [((8800, 128), (3, 128)), ((777, 2048), (3, 8))], ids=["same_c", "c2048_then_8"])
+def test_workspace_reuse_after_a_fuller_call(hip, full, sparse):
+    """A call whose row groups are mostly empty (3 rows: groups 1..63 sum nothing) right after one that filled every
+    partial sum, on one stream: the empty groups must write zeros over the previous call's partial sums.  Through ops.py
+    (the allocator hands the freed workspace out again) and through the C ABI with ONE workspace for all calls."""
+    ops = _ops()
+    big, _ = bn_case(*full, "relu_res")
+    small, stat = build_case(*sparse, "relu_res", seed=5)
+    alone = run_device(ops, small)
+    run_device(ops, big)
+    after = run_device(ops, small)
+    assert _same(alone, after) == []
+    check_case("%dx%d-after-%dx%d" % (sparse + full), small, stat, _cpu(after), "device")
+    ws_bytes = hip.frcnn_bn_train_ws_bytes(max(full[1], sparse[1]))
+    ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=DEV)
+    for fused in (True, False):
+        ws.zero_()
+        first = _raw_call(ops, hip, small, ws, ws_bytes, fused)
+        _raw_call(ops, hip, big, ws, ws_bytes, fused)
+        second = _raw_call(ops, hip, small, ws, ws_bytes, fused)
+        assert _same(first, second) == [] and _same(first, alone) == [], "fused=%s" % fused
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("poison", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_columns_are_independent(hip, poison):
+    """One non-finite input in channel j: every output of every other channel keeps its bits (ordinary arithmetic only)."""
+    ops = _ops()
+    inp, _ = bn_case(257, 132, "relu_res")
+    j = 70                                                                     # second column block, lane 6
+    clean = _cpu(run_device(ops, inp))
+    dirty_inp = dict(inp, y=inp["y"].clone())
+    dirty_inp["y"][101, j] = poison
+    dirty = _cpu(run_device(ops, dirty_inp))
+    others = torch.arange(inp["c"]) != j
+    for name in OUTPUTS:
+        assert _bits_equal(clean[name][..., others], dirty[name][..., others]), name
+    assert not bool(torch.isfinite(dirty["mean"][j]))
+
+
+@pytest.mark.gpu
+def test_relu_mask_at_zero(hip):
+    """out == 0 exactly is masked (the mask is out > 0): a constant channel with beta = 0, and a channel whose residual is
+    the exact negation of the normalised value; there d_res, d_beta, d_gamma and dy are 0."""
+    ops = _ops()
+    base, _ = build_case(257, 8, "relu_res", seed=3)
+    const, normal = REGIMES.index("const_big"), REGIMES.index("normal")
+    inp = dict(base, beta=base["beta"].clone(), res=base["res"].clone())
+    inp["beta"][const] = 0.0
+    inp["res"][:, const] = 0.0
+    plain = run_device(ops, dict(inp, res=None, relu=False))                   # the normalised value as the device forms it
+    inp["res"][:, normal] = -plain["out"][:, normal].cpu()
+    got = _cpu(run_device(ops, inp))
+    for ch in (const, normal):
+        assert bool((got["out"][:, ch] == 0).all()), ch
+        assert bool((got["dres"][:, ch] == 0).all()) and bool((got["dy"][:, ch] == 0).all()), ch
+        assert float(got["dbeta"][ch]) == 0.0 and float(got["dgamma"][ch]) == 0.0, ch
+    assert bool((got["out"][:, REGIMES.index("large")] > 0).any())            # the other channels are alive
+
+
+@pytest.mark.gpu
+def test_absent_affine_equals_ones_and_zeros(hip):
+    ops = _ops()
+    inp, _ = bn_case(257, 132, "relu_res")
+    c = inp["c"]
+    for gamma_absent, beta_absent in ((True, True), (True, False), (False, True)):
+        absent = run_device(ops, dict(inp, gamma=None if gamma_absent else inp["gamma"], beta=None if beta_absent else inp["beta"]))
+        explicit = run_device(ops, dict(inp, gamma=torch.ones(c) if gamma_absent else inp["gamma"],
+                                        beta=torch.zeros(c) if beta_absent else inp["beta"]))
+        assert _same(absent, explicit) == [], (gamma_absent, beta_absent)
+
+
+@pytest.mark.gpu
+def test_accumulating_form(hip):
+    """grad_gamma / grad_beta pre-filled: they end as old + d in fp32 exactly, are the returned tensors, dy unchanged."""
+    ops = _ops()
+    inp, _ = bn_case(257, 132, "relu_res")
+    plain = run_device(ops, inp)
+    g = torch.Generator().manual_seed(4)
+    old_g, old_b = torch.randn(inp["c"], generator=g) * 10, torch.randn(inp["c"], generator=g) * 10
+    for fused in (True, False):
+        buf_g, buf_b = old_g.to(DEV), old_b.to(DEV)
+        if fused:
+            acc = run_device(ops, inp, grad_gamma=buf_g, grad_beta=buf_b)
+        else:
+            with _separate_final(ops):
+                acc = run_device(ops, inp, grad_gamma=buf_g, grad_beta=buf_b)
+        assert acc["dgamma"].data_ptr() == buf_g.data_ptr() and acc["dbeta"].data_ptr() == buf_b.data_ptr()
+        assert _bits_equal(buf_g.cpu(), old_g + plain["dgamma"].cpu()) and _bits_equal(buf_b.cpu(), old_b + plain["dbeta"].cpu())
+        assert _same(plain, acc, ("out", "dy", "dres")) == []
+    assert _counters_are_zero(ops)
+
+
+@pytest.mark.gpu
+def test_rejections(hip):
+    """Refused on the host, by ops.py or by FRCNN_REQUIRE / the workspace check: nothing is launched."""
+    ops, err = _ops(), _hip_error()
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    with pytest.raises(err, match="c%4==0"):
+        ops.bn_train_fwd(z(5, 6), z(6), z(6), EPS, MOM)
+    with pytest.raises(err, match="c%4==0"):
+        ops.bn_train_bwd(z(5, 6), None, z(5, 6), z(6), z(6), z(6))
+    with pytest.raises(err, match="residual"):
+        ops.bn_train_fwd(z(5, 8), z(8), z(8), EPS, MOM, residual=z(4, 8))
+    with pytest.raises(err, match="running_mean has 4 elements, expected 8"):
+        ops.bn_train_fwd(z(5, 8), z(8), z(8), EPS, MOM, z(4), z(8))
+    with pytest.raises(err, match="running_var has 12 elements, expected 8"):
+        ops.bn_train_fwd(z(5, 8), z(8), z(8), EPS, MOM, z(8), z(12))
+    with pytest.raises(err, match="grad_gamma and grad_beta"):
+        ops.bn_train_bwd(z(5, 8), None, z(5, 8), z(8), z(8), z(8), grad_gamma=z(8))
+    with pytest.raises(err, match="shape mismatch"):
+        ops.bn_train_bwd(z(4, 8), None, z(5, 8), z(8), z(8), z(8))
+    assert hip.frcnn_bn_train_ws_bytes(0) == 0 and hip.frcnn_bn_train_ws_bytes(-4) == 0
+    assert hip.frcnn_bn_train_counters(0) == 0 and hip.frcnn_bn_train_counters(-4) == 0
+    assert hip.frcnn_bn_train_ws_bytes(8) == 64 * 8 * 2 * 8 + 3 * 8 * 4 and hip.frcnn_bn_train_counters(65) == 2
+    p, s = ops._ptr, ops._stream()
+    y, v, out, dy = z(5, 8), z(8), z(5, 8), z(5, 8)
+    need = hip.frcnn_bn_train_ws_bytes(8)
+    ws = torch.zeros(need, dtype=torch.uint8, device=DEV)
+    err_arg, err_ws = -1, -2                                                   # FRCNN_ERR_ARG, FRCNN_ERR_WS (include/frcnn_hip.h)
+    assert hip.frcnn_bn_train_bwd(p(y), None, p(y), 5, 8, p(v), p(v), p(v), 1, p(dy), None, p(v), p(v), 0, p(ws), need, None, s) == err_arg
+    assert b"out needed for the ReLU mask" in hip.frcnn_last_error()
+    assert hip.frcnn_bn_train_fwd(p(y), 5, 8, p(v), p(v), EPS, MOM, None, None, None, 0, p(out), p(v), p(v), p(ws), need - 1, None, s) == err_ws
+    assert b"workspace" in hip.frcnn_last_error()
+    assert hip.frcnn_bn_train_bwd(p(y), None, p(y), 5, 8, p(v), p(v), p(v), 0, p(dy), None, p(v), p(v), 0, p(ws), need - 1, None, s) == err_ws
+    assert hip.frcnn_bn_train_fwd(p(y), 0, 8, p(v), p(v), EPS, MOM, None, None, None, 0, p(out), p(v), p(v), p(ws), need, None, s) == err_arg
+    torch.cuda.synchronize()
+
+
+# ================================================================================================
+# Module level: autograd_ops._BnTrainFn against a float64 torch.nn.BatchNorm2d on the CPU, three steps
+# ================================================================================================
+# Here the reference computes its own statistics, so the bars above are composed with what the statistics' bars let
+# through (first order; e_m = the save_mean bar, r_i = the relative save_invstd bar, dxhat = invstd e_m + r_i |xhat|):
+#   out      + |alpha| e_m + r_i |t|
+#   d_gamma  + sum |g| dxhat
+#   dy       + |a| (r_i (|g| + |b| + |xhat k|) + dxhat |k| + |xhat| sum(|g| dxhat) / M)
+#   running statistics, per step: the fp32 update's 2u (|(1 - m) old| + |m stat|), the coefficients m and 1 - m rounded
+#            to fp32 (u (|old| + m |stat|)), m times the statistic's bar, and (1 - m) times the bar of the step before.
+# Inputs are N(offset, scale) per channel with |offset| / scale of order 1, as activations are.
+MODULE_SHAPE = (257, 36)
+MODULE_CONFIGS = ["plain", "cma", "no_track", "no_affine", "frozen_weight", "frozen_bias"]
+MODULE_STEPS = 3
+
+
+def _module(config, seed=21):
+    c = MODULE_SHAPE[1]
+    g = torch.Generator().manual_seed(seed)
+    bn = torch.nn.BatchNorm2d(c, eps=EPS, momentum=None if config == "cma" else MOM, affine=config != "no_affine",
+                              track_running_stats=config != "no_track")
+    with torch.no_grad():
+        if bn.affine:
+            bn.weight.copy_(torch.rand(c, generator=g) + 0.5)
+            bn.bias.copy_(torch.randn(c, generator=g))
+        if bn.track_running_stats:
+            bn.running_mean.copy_(torch.randn(c, generator=g))
+            bn.running_var.copy_(torch.rand(c, generator=g) + 0.5)
+    if config == "frozen_weight":
+        bn.weight.requires_grad_(False)
+    if config == "frozen_bias":
+        bn.bias.requires_grad_(False)
+    return bn.train()
+
+
+@functools.lru_cache(maxsize=None)
+def module_case(config):
+    """Three steps of the float64 module on the CPU: per step the inputs, the float64 results and their bars."""
+    rows, c = MODULE_SHAPE
+    ref_bn = _module(config).double()
+    ref_bn.eps = EPS32
+    chain, steps = _chain(rows), []
+    rm_bar, rv_bar = torch.zeros(c, dtype=torch.float64), torch.zeros(c, dtype=torch.float64)
+    for step in range(MODULE_STEPS):
+        g = torch.Generator().manual_seed(900 + step)
+        y = (torch.randn(rows, c, generator=g) * (torch.rand(c, generator=g) * 2.5 + 0.5) + torch.randn(c, generator=g) * 2).contiguous()
+        res, dout = torch.randn(rows, c, generator=g), torch.randn(rows, c, generator=g)
+        stat = statistics(y)
+        if ref_bn.affine:      # keep every pre-activation off the ReLU's kink, where the mask would be a coin toss
+            near = ((y.double() - stat["mean"]) * stat["invstd"] * ref_bn.weight.detach() + ref_bn.bias.detach() + res.double()).abs() < 1e-3
+        else:
+            near = ((y.double() - stat["mean"]) * stat["invstd"] + res.double()).abs() < 1e-3
+        res = torch.where(near, res + 0.25, res)
+        old_rm = ref_bn.running_mean.clone() if ref_bn.track_running_stats else None
+        old_rv = ref_bn.running_var.clone() if ref_bn.track_running_stats else None
+        x = y.double().t().reshape(1, c, rows, 1).requires_grad_(True)
+        r64 = res.double().requires_grad_(True)
+        pre = ref_bn(x).reshape(c, rows).t() + r64
+        assert float(pre.detach().abs().min()) > 5e-4
+        out = torch.relu(pre)
+        for prm in ref_bn.parameters():
+            prm.grad = None
+        out.backward(dout.double())
+        ref = dict(out=out.detach(), dy=x.grad.reshape(c, rows).t(), dres=r64.grad,
+                   dgamma=ref_bn.weight.grad if ref_bn.affine else None, dbeta=ref_bn.bias.grad if ref_bn.affine else None)
+        e_m, r_i = stat["mean_bar"], stat["invstd_bar"] / stat["invstd"]
+        y64, mu, istd = y.double(), stat["mean"], stat["invstd"]
+        gamma = ref_bn.weight.detach() if ref_bn.affine else torch.ones(c, dtype=torch.float64)
+        beta = ref_bn.bias.detach() if ref_bn.affine else torch.zeros(c, dtype=torch.float64)
+        xhat = (y64 - mu) * istd
+        t = xhat * gamma
+        gm = ref["dres"].abs()
+        a, b, k = (gamma * istd).abs(), (ref["dres"].sum(0) / rows).abs(), ((ref["dres"] * xhat).sum(0) / rows).abs()
+        dxhat = istd * e_m + r_i * xhat.abs()
+        via_xhat = (gm * dxhat).sum(0)
+        terms = gm + b + xhat.abs() * k
+        bars = dict(out=4 * U * (t.abs() + beta.abs() + res.double().abs()) + a * e_m + r_i * t.abs(),
+                    dbeta=U * ref["dres"].sum(0).abs() + chain * E53 * gm.sum(0),
+                    dgamma=U * (ref["dres"] * xhat).sum(0).abs() + 4 * U * (gm * xhat.abs()).sum(0) + via_xhat,
+                    dy=16 * U * a * terms + a * (r_i * terms + dxhat * k + xhat.abs() * via_xhat / rows))
+        if ref_bn.track_running_stats:
+            m = MOM if config != "cma" else 1.0 / (step + 1)
+            factor = rows / (rows - 1.0)
+            unb = stat["var"] * factor
+            rm_bar = (1 - m) * rm_bar + 2 * U * (((1 - m) * old_rm).abs() + m * mu.abs()) + U * (old_rm.abs() + m * mu.abs()) + m * e_m
+            rv_bar = (1 - m) * rv_bar + 2 * U * (((1 - m) * old_rv).abs() + m * unb) + U * (old_rv.abs() + m * unb) + \
+                m * (U * unb + stat["varbound"] * factor)
+            ref.update(rm=ref_bn.running_mean.clone(), rv=ref_bn.running_var.clone(), tracked=int(ref_bn.num_batches_tracked))
+            bars.update(rm=rm_bar, rv=rv_bar)
+        steps.append((dict(y=y, res=res, dout=dout), ref, bars))
+    return steps
+
+
+@pytest.mark.parametrize("config", MODULE_CONFIGS)
+def test_cpu_restatement_module_reference(config):
+    """The module-level reference against this file's own restatement stepped by hand: the composed bars hold for the
+    kernel's arithmetic, with the cumulative average's momentum 1 / n and without buffers or affine parameters."""
+    rows, c = MODULE_SHAPE
+    bn = _module(config)
+    rm = bn.running_mean.clone() if bn.track_running_stats else torch.zeros(c)
+    rv = bn.running_var.clone() if bn.track_running_stats else torch.ones(c)
+    for step, (inp, ref, bars) in enumerate(module_case(config)):
+        m = MOM if config != "cma" else 1.0 / (step + 1)
+        got = restate(dict(inp, gamma=bn.weight.detach() if bn.affine else None, beta=bn.bias.detach() if bn.affine else None,
+                           rm=rm, rv=rv, relu=True), m)
+        rm, rv = got["rm"], got["rv"]
+        _check_module(config, step, got, ref, bars, "cpu", track=bn.track_running_stats, affine=bn.affine)
+
+
+def _check_module(config, step, got, ref, bars, side, track, affine):
+    cid = "module-%s-step%d" % (config, step)
+    for name in ("out", "dy") + (("dgamma", "dbeta") if affine else ()) + (("rm", "rv") if track else ()):
+        if ref[name] is None:                      # a frozen parameter has no gradient (the restatement has no autograd)
+            assert config == {"dgamma": "frozen_weight", "dbeta": "frozen_bias"}[name] and (side == "cpu" or got[name] is None)
+            continue
+        _check(cid, name, got[name], ref[name], bars[name], side)
+    assert torch.equal(got["dres"].double(), ref["dres"]), "d_residual is the masked upstream gradient, exactly"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config", MODULE_CONFIGS)
+def test_module_level(hip, config):
+    from faster_rcnn_pytorch_multimodal_amd.nets import autograd_ops
+    bn = _module(config).to(DEV)
+    for step, (inp, ref, bars) in enumerate(module_case(config)):
+        y, res = inp["y"].to(DEV).requires_grad_(True), inp["res"].to(DEV).requires_grad_(True)
+        for prm in bn.parameters():
+            prm.grad = None
+        out = autograd_ops._BnTrainFn.apply(y, res, bn.weight, bn.bias, bn, True)
+        out.backward(inp["dout"].to(DEV))
+        got = dict(out=out, dy=y.grad, dres=res.grad, dgamma=bn.weight.grad if bn.affine else None,
+                   dbeta=bn.bias.grad if bn.affine else None, rm=bn.running_mean, rv=bn.running_var)
+        _check_module(config, step, _cpu(got), ref, bars, "device", track=bn.track_running_stats, affine=bn.affine)
+        if bn.track_running_stats:
+            assert int(bn.num_batches_tracked) == ref["tracked"] == step + 1
+        else:
+            assert bn.running_mean is None and bn.running_var is None and bn.num_batches_tracked is None
+    assert _counters_are_zero(_ops())
