@@ -29,6 +29,7 @@ SOURCES = {
     "dwconv.hip": ["-ffp-contract=off"],
     "dwconv_bwd.hip": ["-ffp-contract=off"],
     "conv_wgrad.hip": [],
+    "conv_wgrad_plan.hip": [],
     "boxes.hip": ["-ffp-contract=off"],
     "topk.hip": ["-ffp-contract=off"],
     "nms.hip": ["-ffp-contract=off"],

@@ -57,7 +57,7 @@ unsigned long long boxes_settings_word();
 unsigned long long wgrad_settings_word();
 
 // frcnn_conv2d_set_autotune state (conv_plan.hip), shared with the filter-gradient kernel's own plan cache
-// (conv_wgrad.hip), which frcnn_conv2d_clear_plans empties as well.
+// (conv_wgrad_plan.hip), which frcnn_conv2d_clear_plans empties as well.
 bool autotune_enabled();
 void clear_wgrad_plans();
 

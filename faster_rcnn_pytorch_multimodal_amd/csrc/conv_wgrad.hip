@@ -16,41 +16,28 @@
 // Two kernels: conv_wgrad_f32 (rounds 1-4: register-staged tiles, slabs added by wgrad_reduce_kernel / wgrad_accumulate_kernel;
 // plans 1 / 2, kept for operands beyond 2 GB, callers without tile counters and A/B) and conv_wgrad_dma_f32 (round 5: LDS-DMA
 // ring, ds_read_b64 fragments, the LAST workgroup of a tile adds the slabs and stores / accumulates itself; plans 3 / 4).
-#include "common.h"
+// This unit holds the kernels and the launch functions that name them; which plan runs for a call, with which workspace, is
+// conv_wgrad_plan.hip's business.
+#include "conv_wgrad.h"
 
 #include <algorithm>
-#include <array>
-#include <atomic>
-#include <map>
-#include <mutex>
-#include <vector>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace frcnn::wgrad;
 
-constexpr int BR = 32;    // pixels per reduction step
-constexpr int NUM_CU = 256;
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
 // tile edge BT = 64 * TI (k rows x q columns), 2 x 2 waves each owning TI x TI MFMA tiles of 32 x 32:
 //   TI = 2: 128 x 128, the arithmetic-intensity choice for large pixel counts;
 //   TI = 1: 64 x 64, four times as many tiles -> fewer pixel splits (less slab traffic, longer K loops) when the
 //           filter is small and the pixel count short (layer3 / layer4 of one frame: M = 2394 / 608).
 
-struct WgradParams {
-  const float* x;
-  const float* dy;
-  float* out;  // dw [K][RSC] (splits == 1) or slabs [splits][K][RSC]
-  int H, W, C, K, R, S, stride, pad, Ho, Wo;
-  int M, Q;  // pixels, R*S*C
-  int steps, steps_per_split;
-  int tiles_k, tiles_q;
-  // conv_wgrad_dma_f32 only
-  float* target;     // mode 0: dw [K][RSC], overwritten; mode 1: the parameter's gradient (K, c_real, R, S), accumulated into
-  int* counters;     // one per tile, zero on entry and on exit (splits > 1)
-  int mode, c_real, N, splits;
-  unsigned xbytes, dybytes;
-};
+// The kernels' parameter types keep their names in this unit's anonymous namespace (the kernel symbols carry them); the
+// fields are conv_wgrad.h's, the launch functions convert at the launch.
+struct WgradParams : WgradArgs {};
+struct WgradGroups : WgradGroupOperands {};
+struct WgradOuts : WgradGroupGrads {};
 
 template <int TI>
 __device__ __forceinline__ void conv_wgrad_body(const WgradParams& p, const float* __restrict__ px,
@@ -439,14 +426,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_dma_f32(const WgradParams p
 // of layer3, lib/nets/resnet.py:131-240): together they have enough output tiles to fill the chip WITHOUT splitting the
 // pixel reduction, so every tile runs the whole M-pixel loop (75 steps instead of ~9) and no slabs are summed afterwards.
 // Group g writes its (K, Q) result to p.out + g * K * Q.
-constexpr int WG_MAX_GROUPS = 24;
-struct WgradGroups {
-  const float* x[WG_MAX_GROUPS];
-  const float* dy[WG_MAX_GROUPS];
-};
-struct WgradOuts {
-  float* grad[WG_MAX_GROUPS];
-};
 template <int TI>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_grouped_f32(const WgradParams p, const WgradGroups g) {
   const int grp = blockIdx.y;
@@ -473,55 +452,37 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-// db[k] = sum_m dy[m][k] in two deterministic passes: BIAS_GROUPS x (K/64) workgroups sum interleaved pixel
-// subsets (4 waves each) into partial[g][k], then one pass adds the groups in g order.
-constexpr int BIAS_GROUPS = 64;
-// Slab sum + layout change + accumulation in one pass: grad (K, c_real, R, S) - a Conv2d / Linear parameter's own layout -
-// += sum_z slabs[z] (K, R, S, C) restricted to the real channels.  One thread per OUTPUT element (coalesced read-modify-write of
-// the gradient); the slab reads stride by C floats (small tensors).  z ascending: deterministic.
+// Where element i of a parameter's gradient (K, c_real, R, S) - a Conv2d / Linear parameter's own layout - lies in the
+// (K, R, S, C) result of the GEMM.  (The DMA kernels' emit goes the other way, from a 16-byte chunk of the result to four
+// gradient elements, and keeps its own arithmetic.)
+__device__ __forceinline__ size_t krsc_index(size_t i, int R, int S, int C, int c_real) {
+  const int s = (int)(i % S);
+  size_t t = i / S;
+  const int r = (int)(t % R);
+  t /= R;
+  const int c = (int)(t % c_real);
+  const int k = (int)(t / c_real);
+  return (((size_t)k * R + r) * S + s) * C + c;
+}
+
+// Slab sum + layout change + accumulation in one pass, for group blockIdx.y of a (grouped) filter gradient: o.grad[g]
+// (K, c_real, R, S) += sum_z slabs[g][z] (K, R, S, C) restricted to the real channels.  One thread per OUTPUT element (coalesced
+// read-modify-write of the gradient); the slab reads stride by C floats (small tensors).  z ascending: deterministic.
 __global__ __launch_bounds__(256) void wgrad_accumulate_kernel(const float* __restrict__ slabs, int splits, int K, int R, int S,
-                                                              int C, int c_real, float* __restrict__ grad) {
+                                                              int C, int c_real, const WgradOuts o) {
   const size_t total = (size_t)K * c_real * R * S, slab = (size_t)K * R * S * C;
+  const float* __restrict__ src0 = slabs + (size_t)blockIdx.y * splits * slab;
+  float* __restrict__ grad = o.grad[blockIdx.y];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int s = (int)(i % S);
-    size_t t = i / S;
-    const int r = (int)(t % R);
-    t /= R;
-    const int c = (int)(t % c_real);
-    const int k = (int)(t / c_real);
-    const size_t src = (((size_t)k * R + r) * S + s) * C + c;
-    float v = slabs[src];
-    for (int z = 1; z < splits; ++z) v += slabs[(size_t)z * slab + src];
+    const size_t src = krsc_index(i, R, S, C, c_real);
+    float v = src0[src];
+    for (int z = 1; z < splits; ++z) v += src0[(size_t)z * slab + src];
     grad[i] += v;
   }
 }
 
-// the same for the grouped filter gradient: one (K, R, S, C) result per group, added into that group's parameter gradient
-__global__ __launch_bounds__(256) void wgrad_accumulate_grouped_kernel(const float* __restrict__ results, int K, int R, int S,
-                                                                      int C, int c_real, const WgradOuts o) {
-  const size_t total = (size_t)K * c_real * R * S, slab = (size_t)K * R * S * C;
-  const float* src0 = results + (size_t)blockIdx.y * slab;
-  float* grad = o.grad[blockIdx.y];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int s = (int)(i % S);
-    size_t t = i / S;
-    const int r = (int)(t % R);
-    t /= R;
-    const int c = (int)(t % c_real);
-    const int k = (int)(t / c_real);
-    grad[i] += src0[(((size_t)k * R + r) * S + s) * C + c];
-  }
-}
-
-__global__ __launch_bounds__(256) void bias_grad_accumulate_kernel(const float* __restrict__ partial, int K, int groups,
-                                                                  float* __restrict__ db) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= K) return;
-  float v = 0.f;
-  for (int g = 0; g < groups; ++g) v += partial[(size_t)g * K + k];
-  db[k] += v;
-}
-
+// db[k] = sum_m dy[m][k] in two deterministic passes: BIAS_GROUPS x (K/64) workgroups sum interleaved pixel
+// subsets (4 waves each) into partial[g][k], then one pass adds the groups in g order.
 __global__ __launch_bounds__(256) void bias_grad_partial_kernel(const float* __restrict__ dy, int M, int K,
                                                                float* __restrict__ partial) {
   __shared__ float part[4][64];
@@ -535,404 +496,96 @@ __global__ __launch_bounds__(256) void bias_grad_partial_kernel(const float* __r
   if (wave == 0 && k < K)
     partial[(size_t)blockIdx.y * K + k] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
-__global__ __launch_bounds__(256) void bias_grad_final_kernel(const float* __restrict__ partial, int K,
+// db[k] = s or db[k] += 0.f + s, s = the groups' partial sums added in g order from partial[0][k].  The accumulating form used
+// to start its sum at 0.f instead: 0.f + s is that sum bit for bit, for s == -0.f (every partial sum a negative zero) too,
+// where it is +0.f - and that is the only s for which the two starts differ.
+__global__ __launch_bounds__(256) void bias_grad_final_kernel(const float* __restrict__ partial, int K, int accumulate,
                                                              float* __restrict__ db) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
   float s = partial[k];
   for (int g = 1; g < BIAS_GROUPS; ++g) s += partial[(size_t)g * K + k];
-  db[k] = s;
+  db[k] = accumulate ? db[k] + (0.f + s) : s;
 }
 
-// Pixel splits for a given tile count: estimated cycles of the slowest CU (two workgroups per CU share the SIMDs)
-// plus the reduction pass.  ti scales the per-step MFMA work (TI*TI tiles per wave).
-int choose_splits(int tiles, int steps, int ti) {
-  int best = 1;
-  double best_t = 1e300;
-  const double step_cyc = 2.0 * 1024.0 * ti * ti;
-  for (int sp = 1; sp <= 64; ++sp) {
-    const int sps = (steps + sp - 1) / sp;
-    const int real = (steps + sps - 1) / sps;
-    if (real != sp) continue;
-    const long rounds = ((long)tiles * real + 2 * NUM_CU - 1) / (2 * NUM_CU);  // two workgroups per CU
-    const double tcyc = rounds * (sps * step_cyc + 6000.0) + (real > 1 ? real * 300.0 : 0.0);
-    if (tcyc < best_t) {
-      best_t = tcyc;
-      best = real;
-    }
+// ---- launches ------------------------------------------------------------------------------------------------------------
+// (not through frcnn::conv::launch_kernel: these launches are no part of the per-dispatch convolution profile)
+constexpr size_t WG_LDS_BYTES = (size_t)WG_LDS_FLOATS * sizeof(float);
+
+// one launch form for the four GEMM kernel families; `extra` are a grouped kernel's pointer blocks
+template <auto Kernel, typename... Extra>
+int launch(const char* name, size_t lds, const WgradArgs& p, dim3 grid, hipStream_t stream, Extra... extra) {
+  if (lds > 0) {
+    const int rc = frcnn::ensure_dynamic_lds<Kernel>(lds, name);
+    if (rc != FRCNN_OK) return rc;
   }
-  return best;
+  hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, stream, WgradParams{p}, extra...);
+  return frcnn::check_launch(name);
 }
 
-// ti: 1 / 2 = conv_wgrad_f32<1 / 2> (+ reduction / accumulation kernels), 3 / 4 = conv_wgrad_dma_f32<1 / 2> (64 / 128 tile,
-// reduction and accumulation in its own epilogue)
-struct WgradPlan {
-  int ti, splits;
+// The one (TI, UNIT) dispatch: f(tile) with tile's TI / UNIT the constants of a tile factor and of "1x1, stride 1, no padding"
+// (the register-staged kernels have no UNIT form and take TI alone)
+template <int TI_, bool UNIT_>
+struct Tile {
+  static constexpr int TI = TI_;
+  static constexpr bool UNIT = UNIT_;
 };
-inline int tile_factor(int ti) { return ti >= 3 ? ti - 2 : ti; }
-inline int tiles_for(int k, int q, int ti) {
-  const int bt = 64 * tile_factor(ti);
-  return ((k + bt - 1) / bt) * ((q + bt - 1) / bt);
+template <typename F>
+int for_tile(int tf, bool unit, F f) {
+  if (tf == 1) return unit ? f(Tile<1, true>{}) : f(Tile<1, false>{});
+  return unit ? f(Tile<2, true>{}) : f(Tile<2, false>{});
 }
-std::atomic<int> g_wgrad_variant{0};   // frcnn_conv2d_wgrad_set_variant: 0 = every kernel, 1 = conv_wgrad_f32 only, 2 = DMA only
-std::atomic<int> g_wgrad_force_ti{0}, g_wgrad_force_splits{0};   // frcnn_conv2d_wgrad_set_plan (tests): 0 = not forced
-
-// Default plan: the 128 x 128 tile and the modelled split; in autotune mode (frcnn_conv2d_set_autotune, shared with the
-// forward kernel) the first call of a shape times both tile sizes around the modelled split and caches the fastest.
-typedef std::array<int, 9> WgradKey;
-std::map<WgradKey, WgradPlan> g_wgrad_plans;
-std::mutex g_wgrad_mutex;
-
-// dma: the LDS-DMA kernels may be used (operands within a 2 GB buffer; a tile counter per tile at hand when splits > 1)
-std::vector<WgradPlan> wgrad_candidates(int k, int q, int steps, bool dma, bool counters) {
-  std::vector<WgradPlan> out;
-  const int variant = g_wgrad_variant.load();
-  for (int ti = 4; ti >= 1; --ti) {
-    if (ti >= 3 && (!dma || variant == 1)) continue;
-    if (ti <= 2 && variant == 2 && dma) continue;
-    const int base = choose_splits(tiles_for(k, q, ti), steps, tile_factor(ti));
-    for (int sp : {base, std::max(1, base / 2), std::min(64, base * 2), 1}) {
-      const int sps = (steps + sp - 1) / sp;
-      const int real = (steps + sps - 1) / sps;
-      bool dup = false;
-      for (const WgradPlan& c : out) dup = dup || (c.ti == ti && c.splits == real);
-      if (ti >= 3 && real > 1 && !counters) continue;
-      if (!dup && (size_t)real * k * q * sizeof(float) <= ((size_t)1 << 28)) out.push_back(WgradPlan{ti, real});
-    }
-  }
-  return out;
-}
-
-bool wgrad_args_ok(int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
-  return n > 0 && h > 0 && w > 0 && c > 0 && (c % 4) == 0 && k > 0 && (k % 4) == 0 && r > 0 && s > 0 && stride > 0 &&
-         pad >= 0 && (h + 2 * pad - r) >= 0 && (w + 2 * pad - s) >= 0;
-}
+inline bool unit_conv(const WgradArgs& p) { return p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0; }
 
 }  // namespace
 
-void frcnn::clear_wgrad_plans() {
-  std::lock_guard<std::mutex> lock(g_wgrad_mutex);
-  g_wgrad_plans.clear();
+namespace frcnn {
+namespace wgrad {
+
+int launch_gemm(const WgradArgs& p, int ti, hipStream_t stream) {
+  const dim3 grid(p.tiles_k * p.tiles_q, 1, p.splits);
+  return for_tile(tile_factor(ti), unit_conv(p), [&](auto t) {
+    using T = decltype(t);
+    return ti >= 3 ? launch<conv_wgrad_dma_f32<T::TI, T::UNIT>>("conv_wgrad_dma_f32", WG_LDS_BYTES, p, grid, stream)
+                   : launch<conv_wgrad_f32<T::TI>>("conv_wgrad_f32", 0, p, grid, stream);
+  });
 }
 
-namespace {
-
-WgradKey wgrad_key(int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
-  return WgradKey{n, h, w, c, k, r, s, stride, pad};
+int launch_gemm_grouped(const WgradArgs& p, int ti, int groups, const WgradGroupOperands& g, const WgradGroupGrads& o,
+                        hipStream_t stream) {
+  const dim3 grid(p.tiles_k * p.tiles_q, groups, 1);
+  const WgradGroups wg{g};
+  return for_tile(tile_factor(ti), unit_conv(p), [&](auto t) {
+    using T = decltype(t);
+    return ti >= 3 ? launch<conv_wgrad_dma_grouped_f32<T::TI, T::UNIT>>("conv_wgrad_dma_grouped_f32", WG_LDS_BYTES, p, grid, stream,
+                                                                       wg, WgradOuts{o})
+                   : launch<conv_wgrad_grouped_f32<T::TI>>("conv_wgrad_grouped_f32", 0, p, grid, stream, wg);
+  });
 }
 
-bool lookup_wgrad(const WgradKey& key, WgradPlan* pl) {
-  std::lock_guard<std::mutex> lock(g_wgrad_mutex);
-  auto it = g_wgrad_plans.find(key);
-  if (it == g_wgrad_plans.end()) return false;
-  *pl = it->second;
-  return true;
+int launch_reduce(const float* slabs, int splits, size_t n4, float* dw, hipStream_t stream) {
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0, stream, slabs,
+                     splits, n4, dw);
+  return frcnn::check_launch("wgrad_reduce_kernel");
 }
 
-size_t slab_bytes_of(const WgradPlan& pl, int k, int q) {
-  return pl.splits > 1 ? (size_t)pl.splits * k * q * sizeof(float) : 0;
+int launch_accumulate(const float* slabs, int splits, const WgradArgs& p, int groups, const WgradGroupGrads& o,
+                      unsigned max_blocks, hipStream_t stream) {
+  const size_t total = (size_t)p.K * p.c_real * p.R * p.S;
+  hipLaunchKernelGGL(wgrad_accumulate_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, max_blocks), groups), dim3(256),
+                     0, stream, slabs, splits, p.K, p.R, p.S, p.C, p.c_real, WgradOuts{o});
+  return frcnn::check_launch("wgrad_accumulate_kernel");
 }
 
-// Shape -> kernel parameters (plan-independent part); false when a tensor is too large for the 32-bit indices
-bool fill_params(WgradParams* p, const float* x, const float* dy, int n, int h, int w, int c, int k, int r, int s, int stride,
-                 int pad) {
-  p->x = x; p->dy = dy; p->out = nullptr; p->target = nullptr; p->counters = nullptr;
-  p->H = h; p->W = w; p->C = c; p->K = k; p->R = r; p->S = s; p->stride = stride; p->pad = pad;
-  p->Ho = (h + 2 * pad - r) / stride + 1;
-  p->Wo = (w + 2 * pad - s) / stride + 1;
-  const long M = (long)n * p->Ho * p->Wo;
-  if (M * (long)k >= (1L << 31) || (long)n * h * w * c >= (1L << 31)) return false;
-  p->M = (int)M;
-  p->N = n;
-  p->Q = r * s * c;
-  p->steps = (p->M + BR - 1) / BR;
-  p->steps_per_split = p->steps;
-  p->tiles_k = p->tiles_q = 0;
-  p->mode = 0; p->c_real = c; p->splits = 1;
-  p->xbytes = (unsigned)std::min<long>((long)n * h * w * c * 4, 0x7fffffffL);
-  p->dybytes = (unsigned)std::min<long>(M * k * 4, 0x7fffffffL);
-  return true;
-}
-// conv_wgrad_dma_f32 addresses its operands as byte offsets into 2 GB buffers (rows past M included: they must not wrap)
-bool dma_ok(const WgradParams& p) {
-  const long lim = (1L << 31) - 64;
-  return ((long)p.M + 2 * BR) * p.K * 4 < lim && ((long)p.M + 2 * BR) * p.C * 4 < lim &&
-         (long)p.N * p.H * p.W * p.C * 4 < lim;
-}
-inline bool unit_conv(const WgradParams& p) { return p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0; }
-
-template <int TI, bool UNIT>
-int launch_dma(const WgradParams& p, dim3 grid, hipStream_t stream) {
-  constexpr size_t lds = (size_t)WG_LDS_FLOATS * sizeof(float);
-  const int rc = frcnn::ensure_dynamic_lds<&conv_wgrad_dma_f32<TI, UNIT>>(lds, "conv_wgrad_dma_f32");
-  if (rc != FRCNN_OK) return rc;
-  hipLaunchKernelGGL((conv_wgrad_dma_f32<TI, UNIT>), grid, dim3(256), lds, stream, p);
-  return frcnn::check_launch("conv_wgrad_dma_f32");
-}
-template <int TI, bool UNIT>
-int launch_dma_grouped(const WgradParams& p, dim3 grid, const WgradGroups& g, const WgradOuts& o, hipStream_t stream) {
-  constexpr size_t lds = (size_t)WG_LDS_FLOATS * sizeof(float);
-  const int rc = frcnn::ensure_dynamic_lds<&conv_wgrad_dma_grouped_f32<TI, UNIT>>(lds, "conv_wgrad_dma_grouped_f32");
-  if (rc != FRCNN_OK) return rc;
-  hipLaunchKernelGGL((conv_wgrad_dma_grouped_f32<TI, UNIT>), grid, dim3(256), lds, stream, p, g, o);
-  return frcnn::check_launch("conv_wgrad_dma_grouped_f32");
-}
-
-// One plan, start to finish.  mode 0: target = dw [K][R][S][C], overwritten; mode 1: target = the parameter's gradient
-// (K, c_real, R, S), accumulated into.  Plans 1 / 2 need the reduction (mode 0, splits > 1) or accumulation (mode 1) kernel
-// behind the main kernel; plans 3 / 4 finish in their own epilogue.
-int run_wgrad(WgradParams p, const WgradPlan& pl, int mode, float* target, int c_real, void* ws, int* counters,
-              hipStream_t stream) {
-  const int bt = 64 * tile_factor(pl.ti);
-  p.tiles_k = (p.K + bt - 1) / bt;
-  p.tiles_q = (p.Q + bt - 1) / bt;
-  p.steps_per_split = (p.steps + pl.splits - 1) / pl.splits;
-  p.splits = pl.splits;
-  p.mode = mode;
-  p.c_real = c_real;
-  const dim3 grid(p.tiles_k * p.tiles_q, 1, pl.splits);
-  if (pl.ti >= 3) {
-    if (pl.splits > 1 && !counters) return frcnn::fail(FRCNN_ERR_ARG, "conv_wgrad_dma_f32: split plan without tile counters");
-    if ((size_t)pl.splits * p.K * p.Q * sizeof(float) >= ((size_t)1 << 31))
-      return frcnn::fail(FRCNN_ERR_ARG, "conv_wgrad_dma_f32: %d slabs of %d x %d floats exceed a 2 GB buffer", pl.splits, p.K, p.Q);
-    p.out = static_cast<float*>(ws);
-    p.target = target;
-    p.counters = counters;
-    const bool unit = unit_conv(p);
-    if (pl.ti == 3) return unit ? launch_dma<1, true>(p, grid, stream) : launch_dma<1, false>(p, grid, stream);
-    return unit ? launch_dma<2, true>(p, grid, stream) : launch_dma<2, false>(p, grid, stream);
-  }
-  p.out = (pl.splits > 1 || mode == 1) ? static_cast<float*>(ws) : target;
-  if (pl.ti == 2) hipLaunchKernelGGL(conv_wgrad_f32<2>, grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL(conv_wgrad_f32<1>, grid, dim3(256), 0, stream, p);
-  int rc = frcnn::check_launch("conv_wgrad_f32");
-  if (rc != FRCNN_OK) return rc;
-  if (mode == 1) {
-    const size_t total = (size_t)p.K * c_real * p.R * p.S;
-    hipLaunchKernelGGL(wgrad_accumulate_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0,
-                       stream, static_cast<const float*>(ws), pl.splits, p.K, p.R, p.S, p.C, c_real, target);
-    return frcnn::check_launch("wgrad_accumulate_kernel");
-  }
-  if (pl.splits > 1) {
-    const size_t n4 = (size_t)p.K * p.Q / 4;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0,
-                       stream, static_cast<const float*>(ws), pl.splits, n4, target);
-    rc = frcnn::check_launch("wgrad_reduce_kernel");
-  }
-  return rc;
-}
-
-// plan without tuning: the 128 x 128 tile and the modelled split - the DMA kernel when it may be used
-WgradPlan default_plan(const WgradParams& p, bool counters) {
-  const int variant = g_wgrad_variant.load();
-  const int sp2 = choose_splits(tiles_for(p.K, p.Q, 2), p.steps, 2);
-  if (variant != 1 && dma_ok(p) && (sp2 == 1 || counters)) return WgradPlan{4, sp2};
-  return WgradPlan{2, sp2};
-}
-// a cached plan is usable for this call (the caller may have no counters; the variant switch may have changed)
-bool plan_usable(const WgradPlan& pl, const WgradParams& p, bool counters) {
-  const int variant = g_wgrad_variant.load();
-  if (pl.ti >= 3) return variant != 1 && dma_ok(p) && (pl.splits == 1 || counters);
-  return variant != 2 || !dma_ok(p);
-}
-
-// Time every candidate twice on the caller's tensors (best-of), outside stream capture only.
-bool tune_wgrad(const WgradParams& p, float* dw, void* ws, size_t ws_avail, int* counters, hipStream_t stream,
-                WgradPlan* best) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return false;
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess) return false;
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return false; }
-  const std::vector<WgradPlan> cands = wgrad_candidates(p.K, p.Q, p.steps, dma_ok(p), counters != nullptr);
-  std::vector<float> best_of(cands.size(), 1e30f);
-  for (int pass = 0; pass < 2; ++pass)
-    for (size_t ci = 0; ci < cands.size(); ++ci) {
-      if (slab_bytes_of(cands[ci], p.K, p.Q) > ws_avail) continue;
-      if (pass == 0 && run_wgrad(p, cands[ci], 0, dw, p.C, ws, counters, stream) != FRCNN_OK) continue;   // warm-up
-      (void)hipEventRecord(e0, stream);
-      bool ok = true;
-      for (int i = 0; i < 3 && ok; ++i) ok = run_wgrad(p, cands[ci], 0, dw, p.C, ws, counters, stream) == FRCNN_OK;
-      (void)hipEventRecord(e1, stream);
-      float ms = 0.f;
-      if (hipEventSynchronize(e1) != hipSuccess || !ok || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) continue;
-      best_of[ci] = std::min(best_of[ci], ms);
-    }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  float best_ms = 1e30f;
-  bool found = false;
-  for (size_t ci = 0; ci < cands.size(); ++ci)
-    if (best_of[ci] < best_ms) { best_ms = best_of[ci]; *best = cands[ci]; found = true; }
-  return found;
-}
-
-int bias_gradient(const float* dy, int M, int k, float* partial, float* db, bool accumulate, hipStream_t stream) {
+int launch_bias_gradient(const float* dy, int M, int k, float* partial, float* db, bool accumulate, hipStream_t stream) {
   hipLaunchKernelGGL(bias_grad_partial_kernel, dim3((k + 63) / 64, BIAS_GROUPS), dim3(256), 0, stream, dy, M, k, partial);
-  int rc = frcnn::check_launch("bias_grad_partial_kernel");
+  const int rc = frcnn::check_launch("bias_grad_partial_kernel");
   if (rc != FRCNN_OK) return rc;
-  if (accumulate) {
-    hipLaunchKernelGGL(bias_grad_accumulate_kernel, dim3((k + 255) / 256), dim3(256), 0, stream, partial, k, BIAS_GROUPS, db);
-    return frcnn::check_launch("bias_grad_accumulate_kernel");
-  }
-  hipLaunchKernelGGL(bias_grad_final_kernel, dim3((k + 255) / 256), dim3(256), 0, stream, partial, k, db);
+  hipLaunchKernelGGL(bias_grad_final_kernel, dim3((k + 255) / 256), dim3(256), 0, stream, static_cast<const float*>(partial), k,
+                     accumulate ? 1 : 0, db);
   return frcnn::check_launch("bias_grad_final_kernel");
 }
 
-}  // namespace
+}  // namespace wgrad
+}  // namespace frcnn
 
-unsigned long long frcnn::wgrad_settings_word() {
-  return (unsigned long long)g_wgrad_variant.load() | ((unsigned long long)g_wgrad_force_ti.load() << 4) |
-         ((unsigned long long)g_wgrad_force_splits.load() << 8);
-}
-
-extern "C" int frcnn_conv2d_wgrad_set_plan(int kernel, int splits) {
-  if (kernel < 0 || kernel > 4 || splits < 0 || splits > 64 || (kernel > 0 && splits < 1))
-    return frcnn::fail(FRCNN_ERR_ARG, "conv2d_wgrad_set_plan: kernel 0 (not forced) or 1..4, 1..64 pixel splits");
-  g_wgrad_force_ti.store(kernel);
-  g_wgrad_force_splits.store(kernel ? splits : 0);
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_conv2d_wgrad_set_variant(int variant) {
-  if (variant < 0 || variant > 2)
-    return frcnn::fail(FRCNN_ERR_ARG, "conv2d_wgrad_set_variant: 0 (every kernel), 1 (conv_wgrad_f32 only), 2 (conv_wgrad_dma_f32 where it applies)");
-  g_wgrad_variant.store(variant);
-  frcnn::clear_wgrad_plans();
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_conv2d_bwd_weight_counters(int c, int k, int r, int s) {
-  if (c <= 0 || k <= 0 || r <= 0 || s <= 0) return 0;
-  return tiles_for(k, r * s * c, 1);
-}
-
-extern "C" size_t frcnn_conv2d_bwd_weight_ws_bytes(int n, int h, int w, int c, int k, int r, int s, int stride,
-                                                   int pad) {
-  if (!wgrad_args_ok(n, h, w, c, k, r, s, stride, pad)) return 0;
-  WgradParams p;
-  if (!fill_params(&p, nullptr, nullptr, n, h, w, c, k, r, s, stride, pad)) return 0;
-  WgradPlan pl;
-  size_t slabs = 0;
-  if (lookup_wgrad(wgrad_key(n, h, w, c, k, r, s, stride, pad), &pl)) slabs = slab_bytes_of(pl, k, p.Q);
-  // room for whatever this call may still choose: the largest candidate of a shape that is about to be tuned, the default
-  // plans (with and without tile counters) otherwise and in case the cached plan is not usable by the caller
-  if (frcnn::autotune_enabled())
-    for (const WgradPlan& cand : wgrad_candidates(k, p.Q, p.steps, dma_ok(p), true)) slabs = std::max(slabs, slab_bytes_of(cand, k, p.Q));
-  slabs = std::max(slabs, slab_bytes_of(default_plan(p, true), k, p.Q));
-  slabs = std::max(slabs, slab_bytes_of(default_plan(p, false), k, p.Q));
-  if (g_wgrad_force_ti.load()) slabs = std::max(slabs, (size_t)std::max(1, std::min(g_wgrad_force_splits.load(), p.steps)) * k * p.Q * sizeof(float));
-  // at least one slab (the accumulating form of plans 1 / 2 reduces from it) + the bias-gradient partials
-  slabs = std::max(slabs, (size_t)k * p.Q * sizeof(float));
-  return frcnn::align_up(slabs, 256) + (size_t)BIAS_GROUPS * k * sizeof(float);
-}
-
-namespace {
-// shared body of frcnn_conv2d_bwd_weight (mode 0) and frcnn_conv2d_bwd_weight_acc (mode 1)
-int bwd_weight(const char* who, int mode, const float* x, const float* dy, float* target, int c_real, float* bias_target, int n,
-               int h, int w, int c, int k, int r, int s, int stride, int pad, void* ws, size_t ws_bytes, int* counters,
-               hipStream_t stream) {
-  WgradParams p;
-  if (!fill_params(&p, x, dy, n, h, w, c, k, r, s, stride, pad)) return frcnn::fail(FRCNN_ERR_ARG, "%s: tensor too large", who);
-  const size_t bias_bytes = bias_target ? (size_t)BIAS_GROUPS * k * sizeof(float) : 0;
-  const size_t slab_room = ws_bytes > bias_bytes ? ((ws_bytes - bias_bytes) / 256) * 256 : 0;   // slabs first, 256-aligned
-  const WgradKey key = wgrad_key(n, h, w, c, k, r, s, stride, pad);
-  WgradPlan pl;
-  bool have = lookup_wgrad(key, &pl) && plan_usable(pl, p, counters != nullptr);
-  if (const int fti = g_wgrad_force_ti.load()) {
-    pl = WgradPlan{fti, std::max(1, std::min(g_wgrad_force_splits.load(), p.steps))};
-    if (pl.ti >= 3 && (!dma_ok(p) || (pl.splits > 1 && !counters)))
-      return frcnn::fail(FRCNN_ERR_ARG, "%s: the forced plan (%d, %d) does not apply to this call", who, pl.ti, pl.splits);
-    have = true;
-  }
-  if (!have && mode == 0 && frcnn::autotune_enabled() && ws && tune_wgrad(p, target, ws, slab_room, counters, stream, &pl)) {
-    std::lock_guard<std::mutex> lock(g_wgrad_mutex);
-    g_wgrad_plans[key] = pl;
-    have = true;
-  }
-  if (!have) pl = default_plan(p, counters != nullptr);
-  size_t slab_bytes = slab_bytes_of(pl, k, p.Q);
-  if (mode == 1 && pl.ti <= 2) slab_bytes = std::max(slab_bytes, (size_t)k * p.Q * sizeof(float));
-  slab_bytes = frcnn::align_up(slab_bytes, 256);
-  const size_t need = slab_bytes + bias_bytes;
-  if (need > 0 && (!ws || ws_bytes < need)) return frcnn::fail(FRCNN_ERR_WS, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
-  int rc = run_wgrad(p, pl, mode, target, c_real, ws, counters, stream);
-  if (rc != FRCNN_OK || !bias_target) return rc;
-  return bias_gradient(dy, p.M, k, reinterpret_cast<float*>(static_cast<char*>(ws) + slab_bytes), bias_target, mode == 1, stream);
-}
-}  // namespace
-
-extern "C" int frcnn_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* db, int n, int h, int w,
-                                       int c, int k, int r, int s, int stride, int pad, void* ws, size_t ws_bytes,
-                                       int* counters, void* stream_) {
-  FRCNN_REQUIRE(x && dy && dw, "conv2d_bwd_weight: null tensor");
-  FRCNN_REQUIRE(wgrad_args_ok(n, h, w, c, k, r, s, stride, pad),
-                "conv2d_bwd_weight: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d (need c%%4==0, k%%4==0)",
-                n, h, w, c, k, r, s, stride, pad);
-  return bwd_weight("conv2d_bwd_weight", 0, x, dy, dw, c, db, n, h, w, c, k, r, s, stride, pad, ws, ws_bytes, counters,
-                    static_cast<hipStream_t>(stream_));
-}
-
-extern "C" int frcnn_conv2d_bwd_weight_acc(const float* x, const float* dy, float* grad_w, int c_real, float* grad_b, int n,
-                                           int h, int w, int c, int k, int r, int s, int stride, int pad, void* ws,
-                                           size_t ws_bytes, int* counters, void* stream_) {
-  FRCNN_REQUIRE(x && dy && grad_w && c_real > 0 && c_real <= c, "conv2d_bwd_weight_acc: null tensor or c_real out of range");
-  FRCNN_REQUIRE(wgrad_args_ok(n, h, w, c, k, r, s, stride, pad),
-                "conv2d_bwd_weight_acc: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d (need c%%4==0, k%%4==0)",
-                n, h, w, c, k, r, s, stride, pad);
-  return bwd_weight("conv2d_bwd_weight_acc", 1, x, dy, grad_w, c_real, grad_b, n, h, w, c, k, r, s, stride, pad, ws, ws_bytes,
-                    counters, static_cast<hipStream_t>(stream_));
-}
-
-// Filter gradients of `groups` convolutions of identical shape in one launch: grad_w[g] (K, c_real, R, S) += dW(x[g], dy[g]).
-// x / dy / grad_w are HOST arrays of device pointers.  No pixel split, fixed summation order: deterministic.  The LDS-DMA kernel
-// adds into the gradients itself; conv_wgrad_grouped_f32 (variant 1, or operands beyond 2 GB) goes through `ws` and
-// wgrad_accumulate_grouped_kernel.
-extern "C" size_t frcnn_conv2d_bwd_weight_acc_grouped_ws_bytes(int groups, int c, int k, int r, int s) {
-  if (groups <= 0 || c <= 0 || k <= 0 || r <= 0 || s <= 0) return 0;
-  return frcnn::align_up((size_t)groups * k * r * s * c * sizeof(float), 256);
-}
-
-extern "C" int frcnn_conv2d_bwd_weight_acc_grouped(const float* const* x, const float* const* dy, float* const* grad_w,
-                                                   int groups, int c_real, int n, int h, int w, int c, int k, int r, int s,
-                                                   int stride, int pad, void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  FRCNN_REQUIRE(x && dy && grad_w && groups > 0 && groups <= WG_MAX_GROUPS && c_real > 0 && c_real <= c,
-                "conv2d_bwd_weight_acc_grouped: bad arguments (1..%d groups)", WG_MAX_GROUPS);
-  FRCNN_REQUIRE(wgrad_args_ok(n, h, w, c, k, r, s, stride, pad),
-                "conv2d_bwd_weight_acc_grouped: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d", n, h, w, c, k,
-                r, s, stride, pad);
-  WgradParams p;
-  FRCNN_REQUIRE(fill_params(&p, nullptr, nullptr, n, h, w, c, k, r, s, stride, pad), "conv2d_bwd_weight_acc_grouped: tensor too large");
-  WgradGroups g;
-  WgradOuts o;
-  for (int i = 0; i < WG_MAX_GROUPS; ++i) {
-    const int j = i < groups ? i : 0;
-    FRCNN_REQUIRE(x[j] && dy[j] && grad_w[j], "conv2d_bwd_weight_acc_grouped: null tensor in group %d", j);
-    g.x[i] = x[j]; g.dy[i] = dy[j]; o.grad[i] = grad_w[j];
-  }
-  // the 128 x 128 tile when the groups together still give every CU a workgroup, else 64 x 64
-  const int ti = (long)tiles_for(k, p.Q, 2) * groups >= NUM_CU ? 2 : 1;
-  const int bt = 64 * ti;
-  p.tiles_k = (p.K + bt - 1) / bt;
-  p.tiles_q = (p.Q + bt - 1) / bt;
-  const dim3 grid(p.tiles_k * p.tiles_q, groups, 1);
-  if (g_wgrad_variant.load() != 1 && dma_ok(p)) {
-    p.mode = 1; p.c_real = c_real; p.splits = 1;
-    const bool unit = unit_conv(p);
-    if (ti == 1) return unit ? launch_dma_grouped<1, true>(p, grid, g, o, stream) : launch_dma_grouped<1, false>(p, grid, g, o, stream);
-    return unit ? launch_dma_grouped<2, true>(p, grid, g, o, stream) : launch_dma_grouped<2, false>(p, grid, g, o, stream);
-  }
-  const size_t need = frcnn_conv2d_bwd_weight_acc_grouped_ws_bytes(groups, c, k, r, s);
-  if (!ws || ws_bytes < need)
-    return frcnn::fail(FRCNN_ERR_WS, "conv2d_bwd_weight_acc_grouped: workspace %zu < %zu bytes", ws_bytes, need);
-  p.out = static_cast<float*>(ws);
-  if (ti == 2) hipLaunchKernelGGL(conv_wgrad_grouped_f32<2>, grid, dim3(256), 0, stream, p, g);
-  else hipLaunchKernelGGL(conv_wgrad_grouped_f32<1>, grid, dim3(256), 0, stream, p, g);
-  int rc = frcnn::check_launch("conv_wgrad_grouped_f32");
-  if (rc != FRCNN_OK) return rc;
-  const size_t total = (size_t)k * c_real * r * s;
-  hipLaunchKernelGGL(wgrad_accumulate_grouped_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048), groups),
-                     dim3(256), 0, stream, static_cast<const float*>(ws), k, r, s, c, c_real, o);
-  return frcnn::check_launch("wgrad_accumulate_grouped_kernel");
-}

@@ -473,20 +473,38 @@ def set_wgrad_plan(kernel, splits=1):
     _hip.check(_hip.load().frcnn_conv2d_wgrad_set_plan(int(kernel), int(splits)), "frcnn_conv2d_wgrad_set_plan")
 
 
-def conv2d_bwd_weight(x, dy, r, s, stride=1, pad=0, want_bias=False):
-    """Returns (dw (K,R,S,C), db (K,) or None)."""
-    lib = _hip.load()
+def _wgrad_operands(who, x, dy, r, s, stride, pad, grad_w=None):
+    """What the filter-gradient wrappers check and log alike: the operands on the device, dy against the forward output's
+    shape, grad_w against (k, c_real <= c, r, s), the call's direct-form FLOPs.  Returns (n, h, w, c, k, c_real)."""
     _dev_f32(x, "x"); _dev_f32(dy, "dy")
     n, h, w, c = x.shape
     k = dy.shape[-1]
     if tuple(dy.shape[:3]) != (n,) + conv_out_hw(h, w, r, s, stride, pad):
-        raise _hip.HipError("conv2d_bwd_weight: dy shape %s does not match the forward output" % (tuple(dy.shape),))
+        raise _hip.HipError("%s: dy shape %s does not match the forward output" % (who, tuple(dy.shape)))
+    c_real = c
+    if grad_w is not None:
+        _dev_f32(grad_w, "grad_w")
+        c_real = grad_w.shape[1]
+        if grad_w.shape[0] != k or c_real > c or grad_w.numel() != k * c_real * r * s:
+            raise _hip.HipError("%s: grad_w %s does not fit k=%d c<=%d r=%d s=%d" % (who, tuple(grad_w.shape), k, c, r, s))
+    _log_flops('wgrad', 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * k * r * s * c)
+    return n, h, w, c, k, c_real
+
+
+def _wgrad_scratch(lib, device, n, h, w, c, k, r, s, stride, pad):
+    """(workspace, its bytes, tile counters) of one frcnn_conv2d_bwd_weight[_acc] call"""
+    ws_bytes = lib.frcnn_conv2d_bwd_weight_ws_bytes(n, h, w, c, k, r, s, stride, pad)
+    ws = _workspace(ws_bytes, device) if ws_bytes else None
+    return ws, ws_bytes, _tile_counters(device, lib.frcnn_conv2d_bwd_weight_counters(c, k, r, s))
+
+
+def conv2d_bwd_weight(x, dy, r, s, stride=1, pad=0, want_bias=False):
+    """Returns (dw (K,R,S,C), db (K,) or None)."""
+    lib = _hip.load()
+    n, h, w, c, k, _ = _wgrad_operands("conv2d_bwd_weight", x, dy, r, s, stride, pad)
     dw = torch.empty((k, r, s, c), dtype=torch.float32, device=x.device)
     db = torch.empty((k,), dtype=torch.float32, device=x.device) if want_bias else None
-    _log_flops('wgrad', 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * k * r * s * c)
-    ws_bytes = lib.frcnn_conv2d_bwd_weight_ws_bytes(n, h, w, c, k, r, s, stride, pad)
-    ws = _workspace(ws_bytes, x.device) if ws_bytes else None
-    counters = _tile_counters(x.device, lib.frcnn_conv2d_bwd_weight_counters(c, k, r, s))
+    ws, ws_bytes, counters = _wgrad_scratch(lib, x.device, n, h, w, c, k, r, s, stride, pad)
     _hip.check(lib.frcnn_conv2d_bwd_weight(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), n, h, w, c, k, r, s, stride, pad,
                                            _ptr(ws), ws_bytes, counters.data_ptr(), _stream()), "frcnn_conv2d_bwd_weight")
     return dw, db
@@ -496,20 +514,10 @@ def conv2d_bwd_weight_acc(x, dy, r, s, grad_w, grad_b=None, stride=1, pad=0):
     """grad_w (K, C_real, R, S) [or (K, C_real) with r = s = 1] += filter gradient, grad_b (K,) += bias gradient: the
     parameter's own gradient buffers, accumulated in place (frcnn_conv2d_bwd_weight_acc)."""
     lib = _hip.load()
-    _dev_f32(x, "x"); _dev_f32(dy, "dy"); _dev_f32(grad_w, "grad_w")
-    n, h, w, c = x.shape
-    k = dy.shape[-1]
-    if tuple(dy.shape[:3]) != (n,) + conv_out_hw(h, w, r, s, stride, pad):
-        raise _hip.HipError("conv2d_bwd_weight_acc: dy shape %s does not match the forward output" % (tuple(dy.shape),))
-    c_real = grad_w.shape[1]
-    if grad_w.shape[0] != k or c_real > c or grad_w.numel() != k * c_real * r * s:
-        raise _hip.HipError("conv2d_bwd_weight_acc: grad_w %s does not fit k=%d c<=%d r=%d s=%d" % (tuple(grad_w.shape), k, c, r, s))
+    n, h, w, c, k, c_real = _wgrad_operands("conv2d_bwd_weight_acc", x, dy, r, s, stride, pad, grad_w)
     if grad_b is not None:
         _dev_f32(grad_b, "grad_b")
-    _log_flops('wgrad', 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * k * r * s * c)
-    ws_bytes = lib.frcnn_conv2d_bwd_weight_ws_bytes(n, h, w, c, k, r, s, stride, pad)
-    ws = _workspace(ws_bytes, x.device)
-    counters = _tile_counters(x.device, lib.frcnn_conv2d_bwd_weight_counters(c, k, r, s))
+    ws, ws_bytes, counters = _wgrad_scratch(lib, x.device, n, h, w, c, k, r, s, stride, pad)
     _hip.check(lib.frcnn_conv2d_bwd_weight_acc(_ptr(x), _ptr(dy), _ptr(grad_w), c_real, _ptr(grad_b), n, h, w, c, k, r, s,
                                                stride, pad, _ptr(ws), ws_bytes, counters.data_ptr(), _stream()),
                "frcnn_conv2d_bwd_weight_acc")
@@ -526,18 +534,16 @@ def conv2d_bwd_weight_acc_grouped(xs, dys, r, s, grads, stride=1, pad=0):
     groups = len(xs)
     if not (0 < groups <= WGRAD_MAX_GROUPS) or len(dys) != groups or len(grads) != groups:
         raise _hip.HipError("conv2d_bwd_weight_acc_grouped: 1..%d groups, same number of x / dy / grad tensors" % WGRAD_MAX_GROUPS)
-    n, h, w, c = xs[0].shape
-    k = dys[0].shape[-1]
-    c_real = grads[0].shape[1]
+    who = "conv2d_bwd_weight_acc_grouped"
+    first = None
     for x, dy, gw in zip(xs, dys, grads):
-        _dev_f32(x, "x"); _dev_f32(dy, "dy"); _dev_f32(gw, "grad_w")
-        if tuple(x.shape) != (n, h, w, c) or tuple(dy.shape) != (n,) + conv_out_hw(h, w, r, s, stride, pad) + (k,):
-            raise _hip.HipError("conv2d_bwd_weight_acc_grouped: every group must have the shape of the first")
-        if gw.shape[0] != k or gw.shape[1] != c_real or c_real > c or gw.numel() != k * c_real * r * s:
-            raise _hip.HipError("conv2d_bwd_weight_acc_grouped: grad_w %s does not fit k=%d c<=%d r=%d s=%d"
-                                % (tuple(gw.shape), k, c, r, s))
+        if x.shape != xs[0].shape or dy.shape != dys[0].shape:
+            raise _hip.HipError("%s: every group must have the shape of the first" % who)
+        n, h, w, c, k, c_real = _wgrad_operands(who, x, dy, r, s, stride, pad, gw)
+        first = first or c_real
+        if c_real != first:
+            raise _hip.HipError("%s: grad_w %s does not fit k=%d c<=%d r=%d s=%d" % (who, tuple(gw.shape), k, c, r, s))
     arr = ctypes.c_void_p * groups
-    _log_flops('wgrad', 2.0 * groups * dys[0].shape[0] * dys[0].shape[1] * dys[0].shape[2] * k * r * s * c)
     ws_bytes = lib.frcnn_conv2d_bwd_weight_acc_grouped_ws_bytes(groups, c, k, r, s)
     ws = _workspace(ws_bytes, xs[0].device)
     _hip.check(lib.frcnn_conv2d_bwd_weight_acc_grouped(arr(*[t.data_ptr() for t in xs]), arr(*[t.data_ptr() for t in dys]),
