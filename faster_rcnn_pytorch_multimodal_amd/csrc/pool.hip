@@ -1,4 +1,5 @@
-// Max-pool 3x3 / stride 2 / pad 1 forward and backward and the stem's channel padding, NHWC.
+// Max-pool 3x3 / stride 2 / pad 1 forward and backward (the ResNet stem), max-pool 2x2 / stride 2 forward (the VGG16
+// body) and the stem's channel padding, NHWC.
 #include "common.h"
 
 #include <algorithm>
@@ -109,6 +110,60 @@ extern "C" int frcnn_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx
   hipLaunchKernelGGL(maxpool3x3s2_bwd_nhwc, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), x, dy, dx, n, h,
                      w, c / 4, ho, wo);
   return frcnn::check_launch("maxpool3x3s2_bwd_nhwc");
+}
+
+// ------------------------------------------------------------------------------------------------
+// MaxPool 2x2 / stride 2, no padding, ceil_mode off, NHWC (lib/nets/vgg16.py:35,46: the 'M' entries of torchvision's
+// configuration 'D').  The windows do not overlap: every input float is read once, so the kernel is four 16-byte loads
+// per 16-byte store and nothing else.  One lane owns one float4 of channels of one output; neighbouring lanes walk the
+// channel axis (a wave reads four runs and writes one run of 1 KB).  The four loads are issued before the first is used.
+// The grid is bounded (kPool2MaxBlocks workgroups) and every lane walks the outputs in a grid-stride loop with 64-bit
+// offsets.  The last row of an odd H and the last column of an odd W lie in no window and are never read.  max is
+// torch's: a NaN in a window makes that output NaN.  (Two outputs per work item measured the same: profiles/vgg16.md.)
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kPool2Threads = 256;
+constexpr int kPool2MaxBlocks = FRCNN_MAXPOOL2X2_MAX_LANES / kPool2Threads;   // 8 workgroups per CU
+
+// torch's update rule (val > max || isnan(val)), pairwise: a NaN on either side wins
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ f32x4 nan_max4(f32x4 a, f32x4 b) {
+  f32x4 m;
+  m[0] = nan_max(a[0], b[0]); m[1] = nan_max(a[1], b[1]); m[2] = nan_max(a[2], b[2]); m[3] = nan_max(a[3], b[3]);
+  return m;
+}
+
+__global__ __launch_bounds__(kPool2Threads) void maxpool2x2s2_nhwc(const f32x4* __restrict__ x, f32x4* __restrict__ y, int H,
+                                                                   int W, int C4, int Ho, int Wo, unsigned long long total) {
+  const unsigned long long row = (unsigned long long)W * C4;        // float4s of one input row
+  for (unsigned long long i = (unsigned long long)blockIdx.x * kPool2Threads + threadIdx.x; i < total;
+       i += (unsigned long long)gridDim.x * kPool2Threads) {
+    const int c4 = (int)(i % C4);
+    unsigned long long p = i / C4;
+    const int wo = (int)(p % Wo);
+    p /= Wo;
+    const int ho = (int)(p % Ho);
+    const unsigned long long n = p / Ho;
+    const f32x4* src = x + ((n * H + 2 * ho) * W + 2 * wo) * C4 + c4;
+    const f32x4 v00 = src[0], v01 = src[C4], v10 = src[row], v11 = src[row + C4];
+    y[i] = nan_max4(nan_max4(v00, v01), nan_max4(v10, v11));
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+}  // namespace
+
+extern "C" int frcnn_maxpool2x2s2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream_) {
+  FRCNN_REQUIRE(x && y, "maxpool2x2s2_fwd: null x / y");
+  FRCNN_REQUIRE(n > 0 && h >= 2 && w >= 2 && c > 0 && c % 4 == 0,
+                "maxpool2x2s2_fwd: bad shape n=%d h=%d w=%d c=%d (n>0, h>=2, w>=2, c%%4==0)", n, h, w, c);
+  FRCNN_REQUIRE(aligned16(x) && aligned16(y), "maxpool2x2s2_fwd: pointers must be 16-byte aligned");
+  const int ho = h / 2, wo = w / 2, c4 = c / 4;
+  const unsigned long long total = (unsigned long long)n * ho * wo * c4;
+  const int blocks = (int)std::min<unsigned long long>((total + kPool2Threads - 1) / kPool2Threads, kPool2MaxBlocks);
+  hipLaunchKernelGGL(maxpool2x2s2_nhwc, dim3(blocks), dim3(kPool2Threads), 0, static_cast<hipStream_t>(stream_),
+                     reinterpret_cast<const f32x4*>(x), reinterpret_cast<f32x4*>(y), h, w, c4, ho, wo, total);
+  return frcnn::check_launch("maxpool2x2s2_nhwc");
 }
 
 extern "C" int frcnn_pad_channels(const float* x, float* y, int64_t pixels, int c, int c_pad, void* stream_) {

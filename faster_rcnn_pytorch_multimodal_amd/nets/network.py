@@ -409,7 +409,11 @@ class Network(nn.Module):
     def _fc7_from_layer4(self, y):
         # layer4 output (R,7,7,2048) -> fc7 in a chip-wide streaming pass (HBM-bound, 120 MB at 300 RoIs), then the
         # heads on fc7 alone: one workgroup per RoI doing both needed 72 us (profiles/r01h_kernel_stats.md)
-        fc7 = ops.spatial_mean(y)
+        return self._heads_on_fc7(ops.spatial_mean(y))
+
+    def _heads_on_fc7(self, fc7):
+        """The detection heads on an inference fc7 (R, C) through the fused head kernel; ``_region_classification`` picks the
+        result up from ``_predictions['_tail']``.  Returns fc7."""
         if uncertainty.enabled():
             return fc7                                  # the heads run in _region_classification (nets/uncertainty.py)
         r, c = fc7.shape

@@ -573,6 +573,31 @@ def maxpool3x3s2_bwd(x, dy):
     return dx
 
 
+# frcnn_maxpool2x2s2_fwd: the most lanes one launch has (include/frcnn_hip.h FRCNN_MAXPOOL2X2_MAX_LANES); more work items
+# than this make every lane walk its loop more than once
+MAXPOOL2X2_MAX_LANES = 2048 * 256
+
+
+def maxpool2x2s2_nhwc(x, out=None):
+    """nn.MaxPool2d(kernel_size=2, stride=2) (ceil_mode off; lib/nets/vgg16.py:35,46) on an NHWC fp32 tensor
+    (frcnn_maxpool2x2s2_fwd): x (N,H,W,C), C % 4 == 0 -> (N, H // 2, W // 2, C).  The trailing row / column of an odd H / W is
+    never read; a NaN in a window gives NaN, as torch does.  ``out``: a tensor of the result's shape to write into."""
+    lib = _hip.load()
+    _dev_f32(x, "maxpool2x2s2_nhwc: x")
+    if x.dim() != 4:
+        raise _hip.HipError("maxpool2x2s2_nhwc: x must be (N,H,W,C), got %s" % (tuple(x.shape),))
+    n, h, w, c = x.shape
+    shape = (n, h // 2, w // 2, c)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _dev_f32(out, "maxpool2x2s2_nhwc: out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _hip.HipError("maxpool2x2s2_nhwc: out must be %s on %s, got %s" % (shape, x.device, tuple(out.shape)))
+    _hip.check(lib.frcnn_maxpool2x2s2_fwd(_ptr(x), _ptr(out), n, h, w, c, _stream()), "frcnn_maxpool2x2s2_fwd")
+    return out
+
+
 # frcnn_dwconv3x3_fwd: outputs along W one lane produces per work item (include/frcnn_hip.h FRCNN_DWCONV_STRIP)
 DWCONV_STRIP = 4
 

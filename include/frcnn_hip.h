@@ -261,6 +261,19 @@ int frcnn_maxpool3x3s2_fwd(const float* x, float* y, int n, int h, int w, int c,
  * maximum (row-major scan, like the index torch stores) is that pixel; gather form, deterministic. */
 int frcnn_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int n, int h, int w, int c, void* stream);
 
+/* nn.MaxPool2d(kernel_size=2, stride=2), no padding, ceil_mode off (lib/nets/vgg16.py:35,46: the 'M' entries of
+ * torchvision's VGG configuration 'D'), NHWC fp32: x (n,h,w,c) -> y (n, h/2, w/2, c),
+ *   y[n,i,j,ch] = max over dy, dx in {0,1} of x[n, 2i+dy, 2j+dx, ch].
+ * The last row of an odd h and the last column of an odd w belong to no window and are never read.  The maximum is exact and
+ * follows torch's rule (val > max || isnan(val)): a NaN anywhere in a window makes that output NaN, +-inf behave as numbers.
+ * The sign of a zero result is not pinned.  One launch on a bounded grid (at most FRCNN_MAXPOOL2X2_MAX_LANES lanes, each
+ * walking the work items - one float4 of channels of one output - in a loop with 64-bit offsets); no
+ * workspace, no LDS, no atomics, no host synchronisation: the call captures into a hipGraph.
+ * FRCNN_ERR_ARG without a launch: a null x / y, n / c < 1, h < 2 or w < 2 (empty output), c % 4 != 0, a pointer that is not
+ * 16-byte aligned. */
+#define FRCNN_MAXPOOL2X2_MAX_LANES (2048 * 256)
+int frcnn_maxpool2x2s2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
+
 /* Depthwise 3x3 convolution, pad 1, stride 1 or 2, with the folded BatchNorm and ReLU6 of MobileNet-v1's conv_dw block:
  * nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False) -> nn.BatchNorm2d (eval) -> nn.ReLU6
  * (lib/nets/mobilenet_v1.py:117-123).  x (n,h,w,c) NHWC, w_rsc (3,3,c) (the module's (c,1,3,3) weight, channel last),
