@@ -59,6 +59,7 @@ PROTOTYPES = {
     "frcnn_maxpool3x3s2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_maxpool3x3s2_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_maxpool2x2s2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "frcnn_maxpool2x2s2_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "frcnn_dwconv3x3_fwd": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 5 + [c_float, c_float, c_int, _P]),
     "frcnn_clamp_max": (c_int, [_P, c_int64, c_float, _P]),
     "frcnn_dwconv3x3_bwd_data": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 5 + [c_float, c_int, _P]),

@@ -1,5 +1,5 @@
-// Max-pool 3x3 / stride 2 / pad 1 forward and backward (the ResNet stem), max-pool 2x2 / stride 2 forward (the VGG16
-// body) and the stem's channel padding, NHWC.
+// Max-pool 3x3 / stride 2 / pad 1 forward and backward (the ResNet stem), max-pool 2x2 / stride 2 forward and backward (the
+// VGG16 body) and the stem's channel padding, NHWC.
 #include "common.h"
 
 #include <algorithm>
@@ -164,6 +164,79 @@ extern "C" int frcnn_maxpool2x2s2_fwd(const float* x, float* y, int n, int h, in
   hipLaunchKernelGGL(maxpool2x2s2_nhwc, dim3(blocks), dim3(kPool2Threads), 0, static_cast<hipStream_t>(stream_),
                      reinterpret_cast<const f32x4*>(x), reinterpret_cast<f32x4*>(y), h, w, c4, ho, wo, total);
   return frcnn::check_launch("maxpool2x2s2_nhwc");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Backward of the 2x2 / stride 2 max-pool.  The windows do not overlap, so the gradient is a routing: the window's winner
+// receives dy, the other three 0.  One lane owns one float4 of channels of one CELL of the ceil(H/2) x ceil(W/2) grid of 2x2
+// input blocks: a full cell is a window (four 16-byte loads of x, one of dy, four 16-byte stores), a cell cut by the trailing
+// row of an odd H or the trailing column of an odd W lies in no window and its one or two pixels are stored as 0 without a
+// load - every element of dx is written by the launch, no memset.  The winner is torch's: scan (0,0), (0,1), (1,0), (1,1),
+// an element takes over when val > max || isnan(val) - the first of equal values, the last NaN, (0,0) of four -inf.
+// relu_mask: x is the ReLU output of the convolution in front of the pool and dx the gradient of its pre-activation - the
+// winner receives dy only if x[winner] > 0 (act_bwd_kernel's v > 0.f ? g : 0.f), so no act_bwd pass over dx follows.
+// No atomics, no LDS, deterministic; the same bounded grid and 64-bit grid-stride loop as the forward.
+// ------------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(kPool2Threads) void maxpool2x2s2_bwd_nhwc(const f32x4* __restrict__ x,
+                                                                       const f32x4* __restrict__ dy, f32x4* __restrict__ dx,
+                                                                       int H, int W, int C4, int Hc, int Wc, int Ho, int Wo,
+                                                                       unsigned long long total, int relu_mask) {
+  const unsigned long long row = (unsigned long long)W * C4;        // float4s of one input row
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (unsigned long long i = (unsigned long long)blockIdx.x * kPool2Threads + threadIdx.x; i < total;
+       i += (unsigned long long)gridDim.x * kPool2Threads) {
+    const int c4 = (int)(i % C4);
+    unsigned long long p = i / C4;
+    const int wc = (int)(p % Wc);
+    p /= Wc;
+    const int hc = (int)(p % Hc);
+    const unsigned long long n = p / Hc;
+    const unsigned long long at = ((n * H + 2 * hc) * W + 2 * wc) * C4 + c4;
+    const bool has_row = 2 * hc + 1 < H, has_col = 2 * wc + 1 < W;
+    if (!(has_row && has_col)) {        // the trailing row / column: in no window
+      dx[at] = zero;
+      if (has_col) dx[at + C4] = zero;
+      if (has_row) dx[at + row] = zero;
+      continue;
+    }
+    const f32x4 v00 = x[at], v01 = x[at + C4], v10 = x[at + row], v11 = x[at + row + C4];
+    const f32x4 g = dy[((n * Ho + hc) * Wo + wc) * C4 + c4];
+    f32x4 d00, d01, d10, d11;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float m = v00[e];
+      int win = 0;
+      if (v01[e] > m || v01[e] != v01[e]) { m = v01[e]; win = 1; }
+      if (v10[e] > m || v10[e] != v10[e]) { m = v10[e]; win = 2; }
+      if (v11[e] > m || v11[e] != v11[e]) { m = v11[e]; win = 3; }
+      const float ge = relu_mask ? (m > 0.f ? g[e] : 0.f) : g[e];
+      d00[e] = win == 0 ? ge : 0.f;
+      d01[e] = win == 1 ? ge : 0.f;
+      d10[e] = win == 2 ? ge : 0.f;
+      d11[e] = win == 3 ? ge : 0.f;
+    }
+    dx[at] = d00;
+    dx[at + C4] = d01;
+    dx[at + row] = d10;
+    dx[at + row + C4] = d11;
+  }
+}
+}  // namespace
+
+extern "C" int frcnn_maxpool2x2s2_bwd(const float* x, const float* dy, float* dx, int n, int h, int w, int c, int relu_mask,
+                                      void* stream_) {
+  FRCNN_REQUIRE(x && dy && dx, "maxpool2x2s2_bwd: null x / dy / dx");
+  FRCNN_REQUIRE(n > 0 && h >= 2 && w >= 2 && c > 0 && c % 4 == 0,
+                "maxpool2x2s2_bwd: bad shape n=%d h=%d w=%d c=%d (n>0, h>=2, w>=2, c%%4==0)", n, h, w, c);
+  FRCNN_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx), "maxpool2x2s2_bwd: pointers must be 16-byte aligned");
+  const int hc = (h + 1) / 2, wc = (w + 1) / 2, c4 = c / 4;
+  const unsigned long long total = (unsigned long long)n * hc * wc * c4;
+  const int blocks = (int)std::min<unsigned long long>((total + kPool2Threads - 1) / kPool2Threads, kPool2MaxBlocks);
+  hipLaunchKernelGGL(maxpool2x2s2_bwd_nhwc, dim3(blocks), dim3(kPool2Threads), 0, static_cast<hipStream_t>(stream_),
+                     reinterpret_cast<const f32x4*>(x), reinterpret_cast<const f32x4*>(dy), reinterpret_cast<f32x4*>(dx), h, w,
+                     c4, hc, wc, h / 2, w / 2, total, relu_mask ? 1 : 0);
+  return frcnn::check_launch("maxpool2x2s2_bwd_nhwc");
 }
 
 extern "C" int frcnn_pad_channels(const float* x, float* y, int64_t pixels, int c, int c_pad, void* stream_) {

@@ -67,6 +67,7 @@ def _defaults():
         FRAMES_IN_FLIGHT=4,      # frames of a pseudo batch in flight as single-chain graphs, one per hardware queue (1: one captured step at a time)
         FUSED_UPDATE=False,      # the weight update as one HIP launch over the gradient bucket (model/train_val.FusedSGD) instead of torch.optim.SGD
         MOBILENET_EN=False,      # not in the reference (it trains --net mobile like any net): let nets/mobilenet_v1.mobilenetv1 run mode='TRAIN' (depthwise gradients in HIP, cfg.MOBILENET.FIXED_LAYERS 1..12).  False: that net is inference only and a TRAIN forward raises
+        VGG16_EN=False,          # not in the reference (it trains --net vgg16 like any net): let nets/vgg16.vgg16 run mode='TRAIN' (2x2 max-pool gradient in HIP, fc6 / fc7 with their dropouts; features[0..9] stay frozen).  False: that net is inference only and a TRAIN forward raises
         LIDAR=dict(BBOX_NORMALIZE_MEANS=(0.0,) * 7, BBOX_NORMALIZE_STDS=(0.1, 0.1, 0.1, 0.2, 0.2, 0.2, 1.0)),
         IMAGE=dict(BBOX_NORMALIZE_MEANS=(0.0, 0.0, 0.0, 0.0), BBOX_NORMALIZE_STDS=(0.1, 0.1, 0.2, 0.2)))
     c.TEST = dict(SCALES=(1.0,), NMS_THRESH=0.6, BBOX_REG=True, HAS_RPN=True, RPN_NMS_THRESH=0.7,

@@ -208,8 +208,9 @@ class TrainStepRunner:
         self.seed_dev = torch.zeros((2,), dtype=torch.int32, device=dev)
         from .. import ops as _ops
         self.wgrad_counters = _ops.CounterArena(dev)      # tile counters of this runner's filter-gradient launches (_step)
-        from ..nets import uncertainty
-        self.uc_seed_dev = torch.zeros((1,), dtype=torch.int32, device=dev) if uncertainty.enabled() else None
+        # the seed word of the step's counter-based draws (uncertainty heads, VGG16's classifier dropouts), rewritten before
+        # every replay; a net that draws nothing gets none and captures the same graph as ever
+        self.uc_seed_dev = torch.zeros((1,), dtype=torch.int32, device=dev) if net.draws_step_randoms() else None
         self.key = (height, width, channels, self.gt_cap, tuple(float(v) for v in self.info))
         self.bn_modules = [m for m in net.modules()
                            if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training and m.track_running_stats]

@@ -2,7 +2,8 @@
 lib/model/train_val.py:458): each node's forward AND backward are libfrcnn_hip.so launches
 (``frcnn_conv2d_fwd / _bwd_data / _bwd_weight``, ``frcnn_act_bwd``, ``frcnn_upsample_bilinear_*``,
 ``frcnn_roi_align_fwd / _bwd``, ``frcnn_rpn_loss``, ``frcnn_det_loss``, and for MobileNet-v1 ``frcnn_dwconv3x3_fwd /
-_bwd_data / _bwd_weight`` and ``frcnn_act_bwd_cap``).  torch.autograd only orders the nodes
+_bwd_data / _bwd_weight`` and ``frcnn_act_bwd_cap``, for VGG16 ``frcnn_maxpool2x2s2_fwd / _bwd`` and
+``frcnn_dropout_fwd / _bwd``).  torch.autograd only orders the nodes
 and owns the ``.grad`` buffers; gradient accumulation inside a residual block is fused into the data-gradient
 kernel's epilogue (``add=``), so a Bottleneck is ONE node.
 
@@ -264,20 +265,27 @@ class _ConvFn(torch.autograd.Function):
             d_conv, d_res = ops.act_bwd(dy, y, scale, relu=relu, want_res=ctx.has_res and need_res)
         else:
             d_conv, d_res = dy, None
-        dx = dw = db = None
-        r, s = w_krsc.shape[1], w_krsc.shape[2]
-        need_b = need_b and bias is not None
-        if need_w or need_b:
-            grads = _wgrad(x, d_conv, r, s, stride, pad, weight if need_w else None, bias if need_b else None)
-            if need_w:
-                dw = grads[0]
-            if need_b:
-                db = grads[-1]
-        if need_x:
-            w_t = _transposed_filter(owner, w_krsc)
-            dx = ops.conv2d_bwd_data(d_conv, w_t, tuple(x.shape), stride=stride, pad=pad,
-                                     w_winograd=_dgrad_winograd(owner, w_t, tuple(x.shape), stride, pad))
+        dx, dw, db = _conv_grads(x, d_conv, weight, bias, w_krsc, stride, pad, owner, need_x, need_w, need_b)
         return dx, d_res, dw, db, None
+
+
+def _conv_grads(x, d_conv, weight, bias, w_krsc, stride, pad, owner, need_x, need_w, need_b):
+    """(dx, dw, db) of one convolution from the gradient of its raw output: the filter and bias gradients where the installed
+    schedule puts them (``_wgrad``), then the data gradient.  None for what is not needed."""
+    dx = dw = db = None
+    r, s = w_krsc.shape[1], w_krsc.shape[2]
+    need_b = need_b and bias is not None
+    if need_w or need_b:
+        grads = _wgrad(x, d_conv, r, s, stride, pad, weight if need_w else None, bias if need_b else None)
+        if need_w:
+            dw = grads[0]
+        if need_b:
+            db = grads[-1]
+    if need_x:
+        w_t = _transposed_filter(owner, w_krsc)
+        dx = ops.conv2d_bwd_data(d_conv, w_t, tuple(x.shape), stride=stride, pad=pad,
+                                 w_winograd=_dgrad_winograd(owner, w_t, tuple(x.shape), stride, pad))
+    return dx, dw, db
 
 
 class _BnTrainFn(torch.autograd.Function):
@@ -650,6 +658,73 @@ class _MaxPoolFn(torch.autograd.Function):
 
 def maxpool_train(x):
     return _MaxPoolFn.apply(x)
+
+
+class _MaxPool2x2Fn(torch.autograd.Function):
+    """nn.MaxPool2d(2, 2) of the VGG16 body (lib/nets/vgg16.py:35,46) behind something other than a trained convolution."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.maxpool2x2s2_nhwc(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool2x2s2_bwd(x, dy.contiguous())
+
+
+def maxpool2x2_train(x):
+    return _MaxPool2x2Fn.apply(x)
+
+
+class _ConvReluPoolFn(torch.autograd.Function):
+    """p = maxpool2x2(relu(conv(x, w) + b)) as one node (VGG16's features.14 + pool 16, features.21 + pool 23).  y, the ReLU
+    output, is both the pool's input and the ReLU's mask, so the pool's backward writes the gradient of the convolution's raw
+    output directly (``maxpool2x2s2_bwd(relu=True)``): the full-size gradient of y is never written and re-read by an
+    ``act_bwd`` pass."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pack):
+        w_krsc, shift, stride, pad, owner = pack
+        u = _winograd_filter(owner, w_krsc, tuple(x.shape[:3]), stride, pad) if w_krsc.shape[1] == 3 else None
+        y = ops.conv2d_nhwc(x, w_krsc, None, shift, None, stride=stride, pad=pad, relu=True, w_winograd=u)
+        ctx.pack = pack
+        ctx.save_for_backward(x, y, weight, bias)
+        return ops.maxpool2x2s2_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dp):
+        x, y, weight, bias = ctx.saved_tensors
+        w_krsc, _, stride, pad, owner = ctx.pack
+        d_conv = ops.maxpool2x2s2_bwd(y, dp.contiguous(), relu=True)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        dx, dw, db = _conv_grads(x, d_conv, weight, bias, w_krsc, stride, pad, owner, need_x, need_w, need_b)
+        return dx, dw, db, None
+
+
+def conv_relu_pool_train(x, conv):
+    """Differentiable ``MaxPool2d(2, 2)(relu(conv(x)))`` of a convolution with a bias and no BatchNorm."""
+    stride, pad = _stride_pad(conv)
+    w_krsc, scale, shift = prepared_conv(conv, None, False)
+    if scale is not None or x.shape[-1] != w_krsc.shape[-1]:
+        raise NotImplementedError("conv_relu_pool_train: a convolution without BatchNorm on a C % 4 == 0 input")
+    return _ConvReluPoolFn.apply(x, conv.weight, conv.bias, (w_krsc, shift, stride, pad, conv))
+
+
+class _DropoutFn(torch.autograd.Function):
+    """nn.Dropout(p) in train() mode with counter-based masks (frcnn_dropout_fwd / _bwd): the draws use ``seed + *seed_dev``
+    (Network.uc_seed_args), so a captured step draws a new mask per replay."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, stream, seed_dev=None):
+        ctx.meta = (p, seed, stream, seed_dev)
+        return ops.dropout(x.contiguous(), p, seed, stream, seed_dev=seed_dev)
+
+    @staticmethod
+    def backward(ctx, dy):
+        p, seed, stream, seed_dev = ctx.meta
+        return ops.dropout_bwd(dy.contiguous(), p, seed, stream, seed_dev=seed_dev), None, None, None, None
 
 
 class _UpsampleAddFn(torch.autograd.Function):

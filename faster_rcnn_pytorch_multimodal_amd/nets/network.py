@@ -149,6 +149,12 @@ class Network(nn.Module):
         self._uc_calls += 1
         return s
 
+    def draws_step_randoms(self):
+        """Does a training step of this net draw counter-based randoms (dropout masks, logit noise) through
+        ``uc_seed_args``?  A captured step then reads its seed from a device word (model/train_graph.TrainStepRunner) - a
+        host scalar would be baked into the graph and every replay would draw the same values."""
+        return uncertainty.enabled()
+
     def uc_seed_args(self):
         """(seed, seed_dev) for the counter-based draws of this forward: eagerly the host counter (``next_uc_seed``) and no
         device word; inside a captured frame / training step (model/frame_graph.py, model/train_graph.py set

@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..model.config import cfg
-from .autograd_ops import (_BnTrainFn, _Holder, _param_grad_from_krsc, _transposed_filter, _wgrad, linear_train)
+from .autograd_ops import (_BnTrainFn, _DropoutFn, _Holder, _param_grad_from_krsc, _transposed_filter, _wgrad, linear_train)
 from .hip_modules import conv_forward, pad4
 
 # ---- reconstruction constants (the missing network.py) ---------------------------------------------------------------
@@ -270,18 +270,6 @@ def stack_uncertainty_columns(uncertainties, det_roi, num_classes):
 # ---------------------------------------------------------------------------------------------------------------------
 # training
 # ---------------------------------------------------------------------------------------------------------------------
-class _DropoutFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, p, seed, stream, seed_dev=None):
-        ctx.meta = (p, seed, stream, seed_dev)
-        return ops.dropout(x.contiguous(), p, seed, stream, seed_dev=seed_dev)
-
-    @staticmethod
-    def backward(ctx, dy):
-        p, seed, stream, seed_dev = ctx.meta
-        return ops.dropout_bwd(dy.contiguous(), p, seed, stream, seed_dev=seed_dev), None, None, None, None
-
-
 def _branch_train(net, prefix, fc7, epistemic, seed, seed_dev=None):
     if not epistemic:
         return fc7

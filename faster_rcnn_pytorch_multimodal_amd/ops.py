@@ -598,6 +598,30 @@ def maxpool2x2s2_nhwc(x, out=None):
     return out
 
 
+def maxpool2x2s2_bwd(x, dy, relu=False, out=None):
+    """Backward of maxpool2x2s2_nhwc (frcnn_maxpool2x2s2_bwd): x (N,H,W,C) the pooled input, dy (N, H // 2, W // 2, C) -> dx
+    like x.  Per window torch's winner receives dy, everything else - the trailing row / column of an odd H / W included -
+    0: the launch writes every element of dx.  ``relu``: x is a ReLU output and dx the gradient of the ReLU's input (the
+    winner receives dy only if it is > 0), which saves the act_bwd pass.  ``out``: a tensor of x's shape to write into."""
+    lib = _hip.load()
+    _dev_f32(x, "maxpool2x2s2_bwd: x")
+    _dev_f32(dy, "maxpool2x2s2_bwd: dy")
+    if x.dim() != 4:
+        raise _hip.HipError("maxpool2x2s2_bwd: x must be (N,H,W,C), got %s" % (tuple(x.shape),))
+    n, h, w, c = x.shape
+    if tuple(dy.shape) != (n, h // 2, w // 2, c) or dy.device != x.device:
+        raise _hip.HipError("maxpool2x2s2_bwd: dy must be %s on %s, got %s" % ((n, h // 2, w // 2, c), x.device, tuple(dy.shape)))
+    if out is None:
+        out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    else:
+        _dev_f32(out, "maxpool2x2s2_bwd: out")
+        if tuple(out.shape) != tuple(x.shape) or out.device != x.device:
+            raise _hip.HipError("maxpool2x2s2_bwd: out must be %s on %s, got %s" % (tuple(x.shape), x.device, tuple(out.shape)))
+    _hip.check(lib.frcnn_maxpool2x2s2_bwd(_ptr(x), _ptr(dy), _ptr(out), n, h, w, c, int(bool(relu)), _stream()),
+               "frcnn_maxpool2x2s2_bwd")
+    return out
+
+
 # frcnn_dwconv3x3_fwd: outputs along W one lane produces per work item (include/frcnn_hip.h FRCNN_DWCONV_STRIP)
 DWCONV_STRIP = 4
 

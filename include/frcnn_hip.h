@@ -273,6 +273,16 @@ int frcnn_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int n, in
  * 16-byte aligned. */
 #define FRCNN_MAXPOOL2X2_MAX_LANES (2048 * 256)
 int frcnn_maxpool2x2s2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
+/* Its backward: x (n,h,w,c) the pooled input, dy (n, h/2, w/2, c) -> dx (n,h,w,c).  Per window the winner receives dy and the
+ * other three elements 0.f; the winner is torch's (scan (0,0), (0,1), (1,0), (1,1); an element takes over when
+ * val > max || isnan(val)): the first of equal values, the last NaN, element (0,0) of four -inf.  relu_mask != 0: x is the
+ * ReLU output in front of the pool and the winner receives dy only if x[winner] > 0 (frcnn_act_bwd's expression), i.e. dx is
+ * the gradient of the ReLU's input.  EVERY element of dx is written by this launch: the trailing row of an odd h and the
+ * trailing column of an odd w receive 0.f (they are never read from x) - no memset, no workspace, no LDS, no atomics,
+ * deterministic; the call captures into a hipGraph.  Work item: one float4 of channels of one cell of the
+ * ceil(h/2) x ceil(w/2) grid, on the forward's bounded grid (FRCNN_MAXPOOL2X2_MAX_LANES).  FRCNN_ERR_ARG without a launch: the
+ * forward's rules, for x, dy and dx. */
+int frcnn_maxpool2x2s2_bwd(const float* x, const float* dy, float* dx, int n, int h, int w, int c, int relu_mask, void* stream);
 
 /* Depthwise 3x3 convolution, pad 1, stride 1 or 2, with the folded BatchNorm and ReLU6 of MobileNet-v1's conv_dw block:
  * nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False) -> nn.BatchNorm2d (eval) -> nn.ReLU6
