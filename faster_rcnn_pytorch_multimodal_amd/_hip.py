@@ -56,6 +56,11 @@ PROTOTYPES = {
     "frcnn_conv2d_bwd_weight_acc": (c_int, [_P, _P, _P, c_int, _P] + [c_int] * 9 + [_P, c_size_t, _P, _P]),
     "frcnn_conv2d_bwd_weight_acc_grouped_ws_bytes": (c_size_t, [c_int] * 5),
     "frcnn_conv2d_bwd_weight_acc_grouped": (c_int, [_P, _P, _P, c_int, c_int] + [c_int] * 9 + [_P, c_size_t, _P]),
+    "frcnn_conv2d_bwd_data_bf16_ws_bytes": (c_size_t, [c_int] * 9),
+    "frcnn_conv2d_bwd_data_bf16": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P, c_size_t, _P]),
+    "frcnn_conv2d_bwd_weight_bf16_ws_bytes": (c_size_t, [c_int] * 10),
+    "frcnn_conv2d_bwd_weight_bf16": (c_int, [_P, _P, _P, _P] + [c_int] * 10 + [_P, c_size_t, _P]),
+    "frcnn_conv2d_bwd_weight_acc_bf16": (c_int, [_P, _P, _P, c_int, _P] + [c_int] * 10 + [_P, c_size_t, _P]),
     "frcnn_maxpool3x3s2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_maxpool3x3s2_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_maxpool2x2s2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),

@@ -123,6 +123,50 @@ extern "C" int frcnn_conv2d_bwd_data_act(const float* dy, const float* w_crsk_fl
                   static_cast<char*>(ws) + dil, ws_bytes - dil, stream, 1, 0, 0, nullptr, act_y, act_scale);
 }
 
+// bf16-operand data gradient (cfg.TRAIN.CONV_BF16): the same two forms - stride 1, and the zero-inserted strided R x S - as
+// ONE frcnn_conv2d_fwd_bf16 launch of dy (or the zero-inserted dy) with the bf16 pack of the flipped / transposed filter, `add`
+// as that kernel's residual operand.  The act_y mask and act_scale are frcnn_act_bwd in place behind the GEMM (the bf16 kernel's
+// store has no mask operand).  The strided 1x1 form writes a scattered output, which the bf16 kernel does not have: FRCNN_ERR_ARG.
+extern "C" size_t frcnn_conv2d_bwd_data_bf16_ws_bytes(int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
+  if (!dgrad_args_ok(n, h, w, c, k, r, s, stride, pad)) return 0;
+  const DgradGeom g = dgrad_geom(h, w, r, s, stride, pad);
+  return g.dilate ? frcnn::align_up((size_t)n * g.hd * g.wd * k * sizeof(float), 256) : 0;
+}
+
+extern "C" int frcnn_conv2d_bwd_data_bf16(const float* dy, const void* w_crsk_flipped_bf16, const float* add, const float* act_y,
+                                          const float* act_scale, float* dx, int n, int h, int w, int c, int k, int r, int s,
+                                          int stride, int pad, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FRCNN_REQUIRE(dy && w_crsk_flipped_bf16 && dx, "conv2d_bwd_data_bf16: null tensor");
+  FRCNN_REQUIRE(!act_scale || act_y, "conv2d_bwd_data_bf16: act_scale without act_y");
+  FRCNN_REQUIRE(dgrad_args_ok(n, h, w, c, k, r, s, stride, pad) && (k % 32) == 0,
+                "conv2d_bwd_data_bf16: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d (need c%%4==0, k%%32==0, "
+                "r==s, pad<=r-1)", n, h, w, c, k, r, s, stride, pad);
+  FRCNN_REQUIRE(stride == 1 || r > 1, "conv2d_bwd_data_bf16: the strided 1x1 data gradient (scattered output) has no bf16 form");
+  const DgradGeom g = dgrad_geom(h, w, r, s, stride, pad);
+  const size_t need = frcnn_conv2d_bwd_data_bf16_ws_bytes(n, h, w, c, k, r, s, stride, pad);
+  if (need > 0 && (!ws || ws_bytes < need))
+    return frcnn::fail(FRCNN_ERR_WS, "conv2d_bwd_data_bf16: workspace %zu < %zu bytes", ws_bytes, need);
+  const float* src = dy;
+  int hs = g.ho, wsrc = g.wo;
+  if (g.dilate) {
+    float* dyd = static_cast<float*>(ws);
+    const size_t total = (size_t)n * g.hd * g.wd * (k / 4);
+    hipLaunchKernelGGL(dilate_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, stream, dy,
+                       dyd, n, g.ho, g.wo, k / 4, stride, g.hd, g.wd);
+    const int rc = frcnn::check_launch("dilate_kernel");
+    if (rc != FRCNN_OK) return rc;
+    src = dyd;
+    hs = g.hd;
+    wsrc = g.wd;
+  }
+  // dx (n,h,w,c) = conv(src (n,hs,wsrc,k), w^T flipped), same-size output
+  const int rc = frcnn_conv2d_fwd_bf16(src, w_crsk_flipped_bf16, nullptr, nullptr, add, dx, n, hs, wsrc, k, c, r, s, 1, g.pad_t, 0,
+                                       stream_);
+  if (rc != FRCNN_OK || !act_y) return rc;
+  return frcnn_act_bwd(dx, act_y, act_scale, 1, (int64_t)n * h * w, c, dx, nullptr, stream_);
+}
+
 extern "C" int frcnn_conv2d_bwd_data_pre(const float* dy, const float* w_crsk_flipped, const float* w_winograd,
                                          const float* add, float* dx, int n, int h, int w, int c, int k, int r, int s,
                                          int stride, int pad, void* ws, size_t ws_bytes, void* stream_) {

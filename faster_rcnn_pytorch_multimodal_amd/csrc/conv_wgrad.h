@@ -37,12 +37,16 @@ struct WgradGroupGrads {
 };
 
 // ti: 1 / 2 = conv_wgrad_f32<1 / 2> (+ reduction / accumulation kernels), 3 / 4 = conv_wgrad_dma_f32<1 / 2> (64 / 128 tile,
-// reduction and accumulation in its own epilogue)
+// reduction and accumulation in its own epilogue), 5 = conv_wgrad_bf16 (bf16 operands, 128 tile, + reduction / accumulation
+// kernels like 1 / 2)
 struct WgradPlan {
   int ti, splits;
 };
+constexpr int PLAN_BF16 = 5;
+// the main kernel leaves slabs (or, unsplit and overwriting, dw itself) and the reduction / accumulation kernels finish
+inline bool finishes_through_slabs(int ti) { return ti <= 2 || ti == PLAN_BF16; }
 // tile edge 64 * tile_factor(ti), k rows x q columns
-inline int tile_factor(int ti) { return ti >= 3 ? ti - 2 : ti; }
+inline int tile_factor(int ti) { return ti == PLAN_BF16 ? 2 : ti >= 3 ? ti - 2 : ti; }
 inline int tiles_along(int extent, int tf) { return (extent + 64 * tf - 1) / (64 * tf); }
 inline int tiles_for(int k, int q, int ti) { return tiles_along(k, tile_factor(ti)) * tiles_along(q, tile_factor(ti)); }
 inline void set_tiles(WgradArgs& p, int tf) {

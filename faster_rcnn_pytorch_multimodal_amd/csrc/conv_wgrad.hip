@@ -16,6 +16,8 @@
 // Two kernels: conv_wgrad_f32 (rounds 1-4: register-staged tiles, slabs added by wgrad_reduce_kernel / wgrad_accumulate_kernel;
 // plans 1 / 2, kept for operands beyond 2 GB, callers without tile counters and A/B) and conv_wgrad_dma_f32 (round 5: LDS-DMA
 // ring, ds_read_b64 fragments, the LAST workgroup of a tile adds the slabs and stores / accumulates itself; plans 3 / 4).
+// A third, conv_wgrad_bf16 (plan 5), rounds both operands to bf16 and runs on v_mfma_f32_32x32x16_bf16: only for callers that
+// ask for that arithmetic (frcnn_conv2d_bwd_weight_bf16 / _acc_bf16).
 // This unit holds the kernels and the launch functions that name them; which plan runs for a call, with which workspace, is
 // conv_wgrad_plan.hip's business.
 #include "conv_wgrad.h"
@@ -439,6 +441,164 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_dma_grouped_f32(const Wgrad
   conv_wgrad_dma_body<TI, UNIT>(p, g.x[grp], g.dy[grp], o.grad[grp], wg_smem);
 }
 
+// ------------------------------------------------------------------------------------------------
+// bf16-operand form of the filter gradient (plan code 5; cfg.TRAIN.CONV_BF16):
+//
+//     dw[k][q] = sum over pixels m of  bf16(dy)[m][k] * bf16(patch(x))[m][q],   fp32 accumulation
+//
+// on v_mfma_f32_32x32x16_bf16.  The instruction wants 8 consecutive REDUCTION elements (pixels) per lane, the operands are
+// contiguous along k / q: the tiles are transposed on the way into LDS.  A thread loads a 4 pixel x 4 k (q) patch as four
+// 16-byte chunks (one per pixel; the eight threads of a pixel group cover 128 contiguous bytes of a pixel row), rounds it to
+// bf16 once (nearest even, v_cvt_pk_bf16_f32) and stores it as four 8-byte columns - row k (q), pixels 4 pg .. 4 pg + 3 - of a
+// [128 k (q)][32 pixels] bf16 image with the forward bf16 kernel's 80-byte row pitch.  A fragment is then that kernel's
+// ds_read_b128: lane l holds row l & 31, pixels 8 (l >> 5) + j of a group of 16.
+//   LDS banks: a wave's ds_write_b64 goes to rows 4 ch + e (ch = 8 consecutive chunks) at byte 8 pg: word (4 ch + e) 20 + 2 pg,
+//   i.e. bank 16 (ch & 1) + 2 pg + const - all 32 banks, four lanes each: the minimum for 64 lanes x 8 bytes.
+//   Pixel addresses of x advance by carries (no division in the loop), as in conv_wgrad_dma_f32.
+// One tile: 128 x 128, 2 x 2 waves of 64 x 64, one reduction step (BR = 32 pixels = two MFMA groups) prefetched in registers,
+// two LDS stages (40 KB), one barrier per step.  The pixel range is split over gridDim.z into fp32 slabs like conv_wgrad_f32;
+// wgrad_reduce_kernel / wgrad_accumulate_kernel add them in z order: the result is a fixed function of the inputs and the
+// split count.  No last-arriver epilogue, no grouped form, no counters, no atomics.
+// ------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+constexpr int WB_BT = 128;      // tile edge
+constexpr int WB_PITCH = 80;    // bytes per LDS row: 32 pixels of bf16 + 16 B pad (conv_igemm_bf16's BF16_PITCH)
+constexpr int WB_STAGE = WB_BT * WB_PITCH;
+
+__global__ __launch_bounds__(256, 2) void conv_wgrad_bf16(const WgradParams p) {
+  static_assert(BR == 32, "a reduction step is one 64-byte LDS row of bf16 pixels");
+  __shared__ __attribute__((aligned(16))) char As[2 * WB_STAGE];   // dy tile [k][pixel]
+  __shared__ __attribute__((aligned(16))) char Bs[2 * WB_STAGE];   // x tile  [q][pixel]
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int tile_k = blockIdx.x / p.tiles_q, tile_q = blockIdx.x - tile_k * p.tiles_q;
+  const int k0 = tile_k * WB_BT, q0 = tile_q * WB_BT;
+  const int step_begin = blockIdx.z * p.steps_per_split;
+  const int step_end = min(step_begin + p.steps_per_split, p.steps);
+
+  // staging: thread t moves chunk ch (4 k / 4 q) of the four pixels of group pg
+  const int pg = t & 7, ch = t >> 3;
+  const int ka = k0 + ch * 4;
+  const bool ka_ok = ka < p.K;           // K % 4 == 0: a chunk is all in or all out
+  const int qb = q0 + ch * 4;
+  const bool qb_ok = qb < p.Q;           // C % 4 == 0: a chunk lies inside one filter tap
+  const int tap = qb_ok ? qb / p.C : 0;
+  const int cb = qb - tap * p.C;
+  const int tr = tap / p.S, ts = tap - tr * p.S;
+
+  // first pixel of this thread in the current step, as (m, img, ho, wo); a step is BR pixels further
+  int m = step_begin * BR + pg * 4;
+  int img = m / (p.Ho * p.Wo);
+  int ho, wo;
+  {
+    const int rem = m - img * p.Ho * p.Wo;
+    ho = rem / p.Wo;
+    wo = rem - ho * p.Wo;
+  }
+  const int d_img = BR / (p.Ho * p.Wo), d_rem = BR - d_img * p.Ho * p.Wo;
+  const int d_ho = d_rem / p.Wo, d_wo = d_rem - d_ho * p.Wo;
+
+  f32x4 ra[4], rb[4];
+  // (called for consecutive steps: the pixel state advances by one step per call)
+  auto load_tiles = [&]() {
+    int mi = m, ii = img, hh = ho, ww = wo;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool m_ok = mi < p.M;
+      ra[i] = (m_ok && ka_ok) ? *reinterpret_cast<const f32x4*>(p.dy + (size_t)mi * p.K + ka) : f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      const int hi = hh * p.stride - p.pad + tr, wi = ww * p.stride - p.pad + ts;
+      if (m_ok && qb_ok && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
+        v = *reinterpret_cast<const f32x4*>(p.x + ((size_t)(ii * p.H + hi) * p.W + wi) * p.C + cb);
+      rb[i] = v;
+      ++mi;
+      if (++ww == p.Wo) {
+        ww = 0;
+        if (++hh == p.Ho) { hh = 0; ++ii; }
+      }
+    }
+    m += BR;
+    wo += d_wo;
+    ho += d_ho;
+    img += d_img;
+    if (wo >= p.Wo) { wo -= p.Wo; ++ho; }
+    if (ho >= p.Ho) { ho -= p.Ho; ++img; }
+  };
+  // element e of the four chunks = row (ch * 4 + e), pixels 4 pg .. 4 pg + 3
+  auto store_tiles = [&](int buf) {
+    char* a = As + buf * WB_STAGE + (ch * 4) * WB_PITCH + pg * 8;
+    char* b = Bs + buf * WB_STAGE + (ch * 4) * WB_PITCH + pg * 8;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const f32x4 ca = {ra[0][e], ra[1][e], ra[2][e], ra[3][e]};
+      const f32x4 cbv = {rb[0][e], rb[1][e], rb[2][e], rb[3][e]};
+      *reinterpret_cast<bf16x4*>(a + e * WB_PITCH) = __builtin_convertvector(ca, bf16x4);
+      *reinterpret_cast<bf16x4*>(b + e * WB_PITCH) = __builtin_convertvector(cbv, bf16x4);
+    }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // fragment: row l31 of a 32-row block, pixels 8 lh .. 8 lh + 7 of MFMA group kk (16 pixels = 32 bytes)
+  const int frag = l31 * WB_PITCH + 16 * lh;
+  const int a_frag = (wr * 64) * WB_PITCH + frag;
+  const int b_frag = (wc * 64) * WB_PITCH + frag;
+
+  if (step_begin < step_end) {
+    load_tiles();
+    store_tiles(0);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int step = step_begin; step < step_end; ++step) {
+    const bool more = step + 1 < step_end;
+    if (more) load_tiles();
+    const char* Ab = As + cur * WB_STAGE + a_frag;
+    const char* Bb = Bs + cur * WB_STAGE + b_frag;
+    bf16x8 fa[2][2], fb[2][2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[kk][i] = *reinterpret_cast<const bf16x8*>(Ab + i * 32 * WB_PITCH + kk * 32);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) fb[kk][j] = *reinterpret_cast<const bf16x8*>(Bb + j * 32 * WB_PITCH + kk * 32);
+    }
+    // A = dy (row = k), B = x (column = q): D column (lane & 31) = q, D row (register) = k, as in conv_wgrad_f32
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk][i], fb[kk][j], acc[i][j], 0, 0, 0);
+    if (more) store_tiles(cur ^ 1);   // stage cur ^ 1 was last read before the previous step's barrier
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  float* out = p.out + (size_t)blockIdx.z * p.K * p.Q;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int q = q0 + (wc * 2 + j) * 32 + l31;
+    if (q >= p.Q) continue;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int k = k0 + (wr * 2 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (k < p.K) out[(size_t)k * p.Q + q] = acc[i][j][r];
+      }
+  }
+}
+
 // dw = sum_z slab[z] (z order), 16 bytes per thread
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slabs, int splits, size_t n4,
                                                           float* __restrict__ dw) {
@@ -544,6 +704,7 @@ namespace wgrad {
 
 int launch_gemm(const WgradArgs& p, int ti, hipStream_t stream) {
   const dim3 grid(p.tiles_k * p.tiles_q, 1, p.splits);
+  if (ti == PLAN_BF16) return launch<conv_wgrad_bf16>("conv_wgrad_bf16", 0, p, grid, stream);
   return for_tile(tile_factor(ti), unit_conv(p), [&](auto t) {
     using T = decltype(t);
     return ti >= 3 ? launch<conv_wgrad_dma_f32<T::TI, T::UNIT>>("conv_wgrad_dma_f32", WG_LDS_BYTES, p, grid, stream)

@@ -15,11 +15,12 @@ namespace {
 using namespace frcnn::wgrad;
 
 // Pixel splits for a given tile count: estimated cycles of the slowest CU (two workgroups per CU share the SIMDs)
-// plus the reduction pass.  ti scales the per-step MFMA work (TI*TI tiles per wave).
-int choose_splits(int tiles, int steps, int ti) {
+// plus the reduction pass.  ti scales the per-step MFMA work (TI*TI tiles per wave); mfma_cyc = cycles of one 32 x 32 MFMA
+// tile over a step's 32 pixels (fp32: 16 x 64; bf16: 2 x 32, modelled, not tuned).
+int choose_splits(int tiles, int steps, int ti, double mfma_cyc = 1024.0) {
   int best = 1;
   double best_t = 1e300;
-  const double step_cyc = 2.0 * 1024.0 * ti * ti;
+  const double step_cyc = 2.0 * mfma_cyc * ti * ti;
   for (int sp = 1; sp <= 64; ++sp) {
     const int sps = (steps + sp - 1) / sp;
     const int real = (steps + sps - 1) / sps;
@@ -53,7 +54,10 @@ bool dma_ok(const WgradArgs& p) {
 // THE rule for "plan pl may run for this call".  The LDS-DMA kernels (3 / 4) need the operands within a 2 GB buffer and, to
 // split, a tile counter per tile from the caller; the variant switch takes out one family - the register-staged one only
 // where the other applies.  A forced plan (frcnn_conv2d_wgrad_set_plan) and the launch itself do not heed the switch.
-bool plan_may_run(const WgradPlan& pl, const WgradArgs& p, bool counters, bool heed_variant = true) {
+// The bf16 kernel (5) computes something else - products of rounded operands: it runs when, and only when, the caller asks
+// for that arithmetic (`bf16`: frcnn_conv2d_bwd_weight_bf16 / _acc_bf16) - never for a tuner, a cached or a forced plan.
+bool plan_may_run(const WgradPlan& pl, const WgradArgs& p, bool counters, bool heed_variant = true, bool bf16 = false) {
+  if (bf16 || pl.ti == PLAN_BF16) return bf16 && pl.ti == PLAN_BF16;
   const int variant = heed_variant ? g_wgrad_variant.load() : 0;
   if (pl.ti >= 3) return variant != 1 && dma_ok(p) && (pl.splits == 1 || counters);
   return variant != 2 || !dma_ok(p);
@@ -101,7 +105,7 @@ size_t bias_bytes_of(int k) { return (size_t)BIAS_GROUPS * k * sizeof(float); }
 // form of plans 1 / 2 reduces from the workspace even when it does not split: at least one slab.
 size_t bias_offset_of(const WgradPlan& pl, bool accumulate, int k, int q) {
   size_t slabs = slab_bytes_of(pl, k, q);
-  if (accumulate && pl.ti <= 2) slabs = std::max(slabs, (size_t)k * q * sizeof(float));
+  if (accumulate && finishes_through_slabs(pl.ti)) slabs = std::max(slabs, (size_t)k * q * sizeof(float));
   return frcnn::align_up(slabs, 256);
 }
 
@@ -127,19 +131,20 @@ bool fill_params(WgradArgs* p, const float* x, const float* dy, int n, int h, in
 }
 
 // One plan, start to finish.  mode 0: target = dw [K][R][S][C], overwritten; mode 1: target = the parameter's gradient
-// (K, c_real, R, S), accumulated into.  Plans 1 / 2 need the reduction (mode 0, splits > 1) or accumulation (mode 1) kernel
-// behind the main kernel; plans 3 / 4 finish in their own epilogue.
+// (K, c_real, R, S), accumulated into.  Plans 1 / 2 / 5 need the reduction (mode 0, splits > 1) or accumulation (mode 1) kernel
+// behind the main kernel; plans 3 / 4 finish in their own epilogue.  bf16: the caller asked for the bf16 arithmetic.
 int run_wgrad(WgradArgs p, const WgradPlan& pl, int mode, float* target, int c_real, void* ws, int* counters,
-              hipStream_t stream) {
-  if (!plan_may_run(pl, p, counters != nullptr, false))
-    return frcnn::fail(FRCNN_ERR_ARG, "conv_wgrad_dma_f32: plan (%d, %d) needs operands within 2 GB and, to split, tile counters",
+              hipStream_t stream, bool bf16 = false) {
+  if (!plan_may_run(pl, p, counters != nullptr, false, bf16))
+    return frcnn::fail(FRCNN_ERR_ARG, "conv_wgrad: plan (%d, %d) may not run for this call (the LDS-DMA kernels need operands "
+                       "within 2 GB and, to split, tile counters; the bf16 kernel runs for the bf16 entry points only)",
                        pl.ti, pl.splits);
   set_tiles(p, tile_factor(pl.ti));
   p.steps_per_split = (p.steps + pl.splits - 1) / pl.splits;
   p.splits = pl.splits;
   p.mode = mode;
   p.c_real = c_real;
-  if (pl.ti >= 3) {
+  if (!finishes_through_slabs(pl.ti)) {
     // (the one limit only the launch ever checked: the kernel addresses its slabs through one buffer, even a single one)
     if ((size_t)pl.splits * p.K * p.Q * sizeof(float) >= ((size_t)1 << 31))
       return frcnn::fail(FRCNN_ERR_ARG, "conv_wgrad_dma_f32: %d slabs of %d x %d floats exceed a 2 GB buffer", pl.splits, p.K, p.Q);
@@ -230,6 +235,44 @@ int bwd_weight(const char* who, int mode, const float* x, const float* dy, float
   if (need > 0 && (!ws || ws_bytes < need)) return frcnn::fail(FRCNN_ERR_WS, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
   int rc = run_wgrad(p, pl, mode, target, c_real, ws, counters, stream);
   if (rc != FRCNN_OK || !bias_target) return rc;
+  return launch_bias_gradient(dy, p.M, k, reinterpret_cast<float*>(static_cast<char*>(ws) + bias_offset), bias_target, mode == 1,
+                              stream);
+}
+
+// ---- bf16 operands (conv_wgrad_bf16, plan 5) --------------------------------------------------------------------------------
+// The plan of a bf16 call: splits > 0 as the caller gives it, clamped to the reduction steps and to the split count that
+// leaves no empty range in front of the last (bf16_plan_ok then refuses what a launch cannot hold); 0 = the split model with
+// the bf16 step cost, within 256 MB of slabs.
+WgradPlan bf16_plan(const WgradArgs& p, int splits) {
+  int sp = splits > 0 ? splits : choose_splits(tiles_for(p.K, p.Q, PLAN_BF16), p.steps, 2, 64.0);
+  sp = std::max(1, std::min(sp, p.steps));
+  while (splits <= 0 && sp > 1 && (size_t)sp * p.K * p.Q * sizeof(float) > ((size_t)1 << 28)) --sp;
+  const int sps = (p.steps + sp - 1) / sp;
+  return WgradPlan{PLAN_BF16, (p.steps + sps - 1) / sps};
+}
+// A caller's split count is taken as given, so it is the caller's to keep within what a launch can hold: gridDim.z and the
+// 256 MB of slabs the library's own choice stays within.
+constexpr int WB_MAX_SPLITS = 65535;
+bool bf16_plan_ok(const WgradPlan& pl, const WgradArgs& p) {
+  return pl.splits <= WB_MAX_SPLITS && (pl.splits == 1 || (size_t)pl.splits * p.K * p.Q * sizeof(float) <= ((size_t)1 << 28));
+}
+
+// shared body of frcnn_conv2d_bwd_weight_bf16 (mode 0) and frcnn_conv2d_bwd_weight_acc_bf16 (mode 1)
+int bwd_weight_bf16(const char* who, int mode, const float* x, const float* dy, float* target, int c_real, float* bias_target,
+                    int n, int h, int w, int c, int k, int r, int s, int stride, int pad, int splits, void* ws, size_t ws_bytes,
+                    hipStream_t stream) {
+  WgradArgs p;
+  if (!fill_params(&p, x, dy, n, h, w, c, k, r, s, stride, pad)) return frcnn::fail(FRCNN_ERR_ARG, "%s: tensor too large", who);
+  const WgradPlan pl = bf16_plan(p, splits);
+  if (!bf16_plan_ok(pl, p))
+    return frcnn::fail(FRCNN_ERR_ARG, "%s: %d pixel splits of %d x %d floats exceed %d launches in z or 256 MB of slabs", who,
+                       pl.splits, p.K, p.Q, WB_MAX_SPLITS);
+  const size_t bias_offset = bias_offset_of(pl, mode == 1, k, p.Q);
+  const size_t need = bias_offset + (bias_target ? bias_bytes_of(k) : 0);
+  if (need > 0 && (!ws || ws_bytes < need)) return frcnn::fail(FRCNN_ERR_WS, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+  const int rc = run_wgrad(p, pl, mode, target, c_real, ws, nullptr, stream, true);
+  if (rc != FRCNN_OK || !bias_target) return rc;
+  // (the bias gradient has no matrix product: fp32 as in the fp32 entry points)
   return launch_bias_gradient(dy, p.M, k, reinterpret_cast<float*>(static_cast<char*>(ws) + bias_offset), bias_target, mode == 1,
                               stream);
 }
@@ -350,4 +393,39 @@ extern "C" int frcnn_conv2d_bwd_weight_acc_grouped(const float* const* x, const 
   const int rc = launch_gemm_grouped(p, tf, groups, g, o, stream);
   if (rc != FRCNN_OK) return rc;
   return launch_accumulate(static_cast<const float*>(ws), 1, p, groups, o, 2048, stream);
+}
+
+// ---- bf16-operand filter gradient (cfg.TRAIN.CONV_BF16) ----------------------------------------------------------------------
+extern "C" size_t frcnn_conv2d_bwd_weight_bf16_ws_bytes(int n, int h, int w, int c, int k, int r, int s, int stride, int pad,
+                                                        int splits) {
+  if (!wgrad_args_ok(n, h, w, c, k, r, s, stride, pad) || splits < 0) return 0;
+  WgradArgs p;
+  if (!fill_params(&p, nullptr, nullptr, n, h, w, c, k, r, s, stride, pad)) return 0;
+  // either form, with the bias gradient (0 for a split count the call would refuse)
+  const WgradPlan pl = bf16_plan(p, splits);
+  if (!bf16_plan_ok(pl, p)) return 0;
+  return bias_offset_of(pl, true, k, p.Q) + bias_bytes_of(k);
+}
+
+extern "C" int frcnn_conv2d_bwd_weight_bf16(const float* x, const float* dy, float* dw, float* db, int n, int h, int w, int c,
+                                            int k, int r, int s, int stride, int pad, int splits, void* ws, size_t ws_bytes,
+                                            void* stream_) {
+  FRCNN_REQUIRE(x && dy && dw && splits >= 0, "conv2d_bwd_weight_bf16: null tensor or negative split count");
+  FRCNN_REQUIRE(wgrad_args_ok(n, h, w, c, k, r, s, stride, pad),
+                "conv2d_bwd_weight_bf16: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d (need c%%4==0, k%%4==0)",
+                n, h, w, c, k, r, s, stride, pad);
+  return bwd_weight_bf16("conv2d_bwd_weight_bf16", 0, x, dy, dw, c, db, n, h, w, c, k, r, s, stride, pad, splits, ws, ws_bytes,
+                         static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int frcnn_conv2d_bwd_weight_acc_bf16(const float* x, const float* dy, float* grad_w, int c_real, float* grad_b, int n,
+                                                int h, int w, int c, int k, int r, int s, int stride, int pad, int splits,
+                                                void* ws, size_t ws_bytes, void* stream_) {
+  FRCNN_REQUIRE(x && dy && grad_w && c_real > 0 && c_real <= c && splits >= 0,
+                "conv2d_bwd_weight_acc_bf16: null tensor, c_real out of range or negative split count");
+  FRCNN_REQUIRE(wgrad_args_ok(n, h, w, c, k, r, s, stride, pad),
+                "conv2d_bwd_weight_acc_bf16: bad shape n=%d h=%d w=%d c=%d k=%d r=%d s=%d stride=%d pad=%d (need c%%4==0, k%%4==0)",
+                n, h, w, c, k, r, s, stride, pad);
+  return bwd_weight_bf16("conv2d_bwd_weight_acc_bf16", 1, x, dy, grad_w, c_real, grad_b, n, h, w, c, k, r, s, stride, pad, splits,
+                         ws, ws_bytes, static_cast<hipStream_t>(stream_));
 }

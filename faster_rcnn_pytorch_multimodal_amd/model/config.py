@@ -68,6 +68,7 @@ def _defaults():
         FUSED_UPDATE=False,      # the weight update as one HIP launch over the gradient bucket (model/train_val.FusedSGD) instead of torch.optim.SGD
         MOBILENET_EN=False,      # not in the reference (it trains --net mobile like any net): let nets/mobilenet_v1.mobilenetv1 run mode='TRAIN' (depthwise gradients in HIP, cfg.MOBILENET.FIXED_LAYERS 1..12).  False: that net is inference only and a TRAIN forward raises
         VGG16_EN=False,          # not in the reference (it trains --net vgg16 like any net): let nets/vgg16.vgg16 run mode='TRAIN' (2x2 max-pool gradient in HIP, fc6 / fc7 with their dropouts; features[0..9] stay frozen).  False: that net is inference only and a TRAIN forward raises
+        CONV_BF16=False,         # not in the reference: in a mode='TRAIN' forward and its backward the convolutions of the Bottleneck and conv_bn_act_train nodes with C % 32 == 0 and K % 32 == 0 round both operands of their forward, data-gradient and filter-gradient products to bf16 and run on v_mfma_f32_32x32x16_bf16 (fp32 accumulation; maps, master weights, gradients, BatchNorm statistics, losses and the solver stay fp32; nets/hip_modules.conv_bf16_train_eligible).  Changes the results (profiles/conv_bf16_train.md)
         LIDAR=dict(BBOX_NORMALIZE_MEANS=(0.0,) * 7, BBOX_NORMALIZE_STDS=(0.1, 0.1, 0.1, 0.2, 0.2, 0.2, 1.0)),
         IMAGE=dict(BBOX_NORMALIZE_MEANS=(0.0, 0.0, 0.0, 0.0), BBOX_NORMALIZE_STDS=(0.1, 0.1, 0.2, 0.2)))
     c.TEST = dict(SCALES=(1.0,), NMS_THRESH=0.6, BBOX_REG=True, HAS_RPN=True, RPN_NMS_THRESH=0.7,

@@ -19,7 +19,8 @@ import os
 import torch
 
 from .. import ops
-from .hip_modules import _winograd_filter, pad4, prepared_conv, prepared_depthwise, stable_store
+from .hip_modules import (_bf16_entry, _winograd_filter, conv_bf16_train_dgrad_fp32, conv_bf16_train_wanted, pad4, prepared_conv,
+                          prepared_depthwise, stable_store)
 
 
 # How one pass launches its filter gradients.  They are off the critical path of backward (only the data gradient feeds the next
@@ -151,14 +152,16 @@ def _accumulate(param, grad):
         param.grad.add_(grad)
 
 
-def _wgrad(x, d_conv, r, s, stride, pad, weight=None, bias=None, mapped=None):
+def _wgrad(x, d_conv, r, s, stride, pad, weight=None, bias=None, mapped=None, bf16=False):
     """Filter (and bias) gradient of one convolution, one list entry per target: the gradients when the schedule returns
     them to autograd, None for each when it accumulates into param.grad.
     Plain case: ``weight`` [, ``bias``] of ONE module (targets in that order), gradients in the parameters' own layout -
     with the gradient buffers in place it is one launch chain that sums the pixel-split slabs, changes the layout and adds
     into param.grad (no temporaries, no permute copy, no add_), and it may join a group.
     Special layouts (the fused head's K-slices, the permuted Linear): ``mapped`` = list of (param, fn), fn maps
-    (dw_krsc, db) to that parameter's gradient; never in place, never grouped."""
+    (dw_krsc, db) to that parameter's gradient; never in place, never grouped.
+    ``bf16`` (cfg.TRAIN.CONV_BF16, an eligible convolution): the bf16-operand kernel, launched layer by layer - it has no grouped
+    form, so the layer skips the grouped deferral."""
     plain = mapped is None
     if plain:
         mapped = [(weight, lambda dwk, dbk: _param_grad_from_krsc(dwk, weight))] if weight is not None else []
@@ -167,14 +170,18 @@ def _wgrad(x, d_conv, r, s, stride, pad, weight=None, bias=None, mapped=None):
     want_bias = bias is not None or not plain
 
     def param_layout_grads():
-        dw_krsc, db = ops.conv2d_bwd_weight(x, d_conv, r, s, stride=stride, pad=pad, want_bias=want_bias)
+        bwd_weight = ops.conv2d_bwd_weight_bf16 if bf16 else ops.conv2d_bwd_weight
+        dw_krsc, db = bwd_weight(x, d_conv, r, s, stride=stride, pad=pad, want_bias=want_bias)
         return [fn(dw_krsc, db) for _, fn in mapped]
 
     if not SCHEDULE.accumulate:
         return param_layout_grads()
     in_place = (plain and weight is not None and all(p.grad is not None and p.grad.is_contiguous() for p, _ in mapped)
                 and weight.dim() in (2, 4) and weight.numel() == d_conv.shape[-1] * weight.shape[1] * r * s)
-    if in_place and SCHEDULE.grouped and bias is None and weight.dim() == 4:
+    if in_place and bf16:
+        _launch_wgrad(weight.grad, [x, d_conv], lambda: ops.conv2d_bwd_weight_acc_bf16(
+            x, d_conv, r, s, weight.grad, bias.grad if bias is not None else None, stride=stride, pad=pad))
+    elif in_place and SCHEDULE.grouped and bias is None and weight.dim() == 4:
         _defer_wgrad(x, d_conv, r, s, stride, pad, weight.grad)
     elif in_place:
         _launch_wgrad(weight.grad, [x, d_conv], lambda: ops.conv2d_bwd_weight_acc(
@@ -193,6 +200,26 @@ def _transposed_filter(conv_like, w_krsc):
         return cache[1][0]
     return stable_store(conv_like, '_frcnn_wt', key, (ops.conv2d_transpose_filter(w_krsc),),
                         refresh=lambda: _transposed_filter(conv_like, w_krsc))[0]
+
+
+def _conv_fwd_bf16(x, prepared, holder, residual, stride, pad, relu):
+    """Forward of an eligible convolution under cfg.TRAIN.CONV_BF16: ``ops.conv2d_nhwc_bf16`` on the packed filter, cached on
+    ``holder`` like the inference path's (``_bf16_entry``: re-packed in place when the weights change; a miss inside a capture
+    raises).  A layer with a Winograd form in fp32 runs as a direct bf16 convolution."""
+    w_krsc, scale, shift = prepared
+    return ops.conv2d_nhwc_bf16(x, _bf16_entry(holder, '_frcnn_bf16', w_krsc), scale, shift, residual, stride=stride, pad=pad,
+                                relu=relu)
+
+
+def _bwd_data_bf16(d, holder, w_krsc, x_shape, stride=1, pad=0, add=None, act_y=None, act_scale=None):
+    """Data gradient of an eligible convolution under cfg.TRAIN.CONV_BF16: the bf16 GEMM on the bf16 pack of the flipped /
+    transposed filter (cached next to ``_frcnn_wt`` under the same rules) - except the strided 1x1 form, whose scattered
+    output the bf16 kernel does not have: that one stays fp32."""
+    w_t = _transposed_filter(holder, w_krsc)
+    if conv_bf16_train_dgrad_fp32(w_krsc.shape[1], w_krsc.shape[2], stride):
+        return ops.conv2d_bwd_data(d, w_t, x_shape, stride=stride, pad=pad, add=add, act_y=act_y, act_scale=act_scale)
+    return ops.conv2d_bwd_data_bf16(d, _bf16_entry(holder, '_frcnn_dgrad_bf16', w_t), x_shape, stride=stride, pad=pad, add=add,
+                                    act_y=act_y, act_scale=act_scale)
 
 
 RELU6_CAP = 6.0                 # nn.ReLU6 of MobileNet-v1 (_SeparablePairFn)
@@ -245,12 +272,17 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, residual, weight, bias, pack):
-        w_krsc, scale, shift, stride, pad, relu, owner = pack
+        w_krsc, scale, shift, stride, pad, relu, owner = pack[:7]
+        # pack[7] (conv_bn_act_train only): the call site is one cfg.TRAIN.CONV_BF16 covers
+        ctx.bf16 = len(pack) > 7 and pack[7] and conv_bf16_train_wanted(w_krsc, stride, pad, any(ctx.needs_input_grad[:4]))
         u = None
-        if residual is None and w_krsc.shape[1] == 3 and isinstance(owner, torch.nn.Module):
-            u = _winograd_filter(owner, w_krsc, tuple(x.shape[:3]), stride, pad)
-        y = ops.conv2d_nhwc(x, w_krsc, scale, shift, residual, stride=stride, pad=pad, relu=relu, w_winograd=u)
-        ctx.pack = pack
+        if ctx.bf16:
+            y = _conv_fwd_bf16(x, (w_krsc, scale, shift), owner, residual, stride, pad, relu)
+        else:
+            if residual is None and w_krsc.shape[1] == 3 and isinstance(owner, torch.nn.Module):
+                u = _winograd_filter(owner, w_krsc, tuple(x.shape[:3]), stride, pad)
+            y = ops.conv2d_nhwc(x, w_krsc, scale, shift, residual, stride=stride, pad=pad, relu=relu, w_winograd=u)
+        ctx.pack = pack[:7]
         ctx.has_res = residual is not None
         ctx.save_for_backward(x, y if relu else None, weight, bias)
         return y
@@ -265,23 +297,25 @@ class _ConvFn(torch.autograd.Function):
             d_conv, d_res = ops.act_bwd(dy, y, scale, relu=relu, want_res=ctx.has_res and need_res)
         else:
             d_conv, d_res = dy, None
-        dx, dw, db = _conv_grads(x, d_conv, weight, bias, w_krsc, stride, pad, owner, need_x, need_w, need_b)
+        dx, dw, db = _conv_grads(x, d_conv, weight, bias, w_krsc, stride, pad, owner, need_x, need_w, need_b, bf16=ctx.bf16)
         return dx, d_res, dw, db, None
 
 
-def _conv_grads(x, d_conv, weight, bias, w_krsc, stride, pad, owner, need_x, need_w, need_b):
+def _conv_grads(x, d_conv, weight, bias, w_krsc, stride, pad, owner, need_x, need_w, need_b, bf16=False):
     """(dx, dw, db) of one convolution from the gradient of its raw output: the filter and bias gradients where the installed
     schedule puts them (``_wgrad``), then the data gradient.  None for what is not needed."""
     dx = dw = db = None
     r, s = w_krsc.shape[1], w_krsc.shape[2]
     need_b = need_b and bias is not None
     if need_w or need_b:
-        grads = _wgrad(x, d_conv, r, s, stride, pad, weight if need_w else None, bias if need_b else None)
+        grads = _wgrad(x, d_conv, r, s, stride, pad, weight if need_w else None, bias if need_b else None, bf16=bf16)
         if need_w:
             dw = grads[0]
         if need_b:
             db = grads[-1]
-    if need_x:
+    if need_x and bf16:
+        dx = _bwd_data_bf16(d_conv, owner, w_krsc, tuple(x.shape), stride=stride, pad=pad)
+    elif need_x:
         w_t = _transposed_filter(owner, w_krsc)
         dx = ops.conv2d_bwd_data(d_conv, w_t, tuple(x.shape), stride=stride, pad=pad,
                                  w_winograd=_dgrad_winograd(owner, w_t, tuple(x.shape), stride, pad))
@@ -356,7 +390,7 @@ def conv_bn_act_train(x, conv, bn=None, relu=False, residual=None, use_bn=True):
         w_krsc, _, shift = prepared_conv(conv, None, False)
         if x.shape[-1] != w_krsc.shape[-1]:
             raise NotImplementedError("differentiable conv needs C % 4 == 0 inputs (only the frozen stem pads its input)")
-        y = _ConvFn.apply(x, None, conv.weight, conv.bias, (w_krsc, None, shift, stride, pad, False, conv))
+        y = _ConvFn.apply(x, None, conv.weight, conv.bias, (w_krsc, None, shift, stride, pad, False, conv, True))
         return _BnTrainFn.apply(y, residual, bn.weight, bn.bias, bn, relu)
     if bn is not None and use_bn and any(p.requires_grad for p in bn.parameters()):
         raise NotImplementedError("trainable BatchNorm affine parameters with frozen (eval-mode) statistics are not on "
@@ -366,7 +400,7 @@ def conv_bn_act_train(x, conv, bn=None, relu=False, residual=None, use_bn=True):
         raise NotImplementedError("differentiable conv needs C % 4 == 0 inputs (only the frozen stem pads its input)")
     # with a folded BN the effective bias is shift = bn.bias - mean*scale (+ conv.bias*scale); conv.bias itself only
     # exists on the BN-free convolutions (RPN, FPN), where shift == conv.bias and d(bias) = sum(d_conv)
-    return _ConvFn.apply(x, residual, conv.weight, conv.bias, (w_krsc, scale, shift, stride, pad, relu, conv))
+    return _ConvFn.apply(x, residual, conv.weight, conv.bias, (w_krsc, scale, shift, stride, pad, relu, conv, True))
 
 
 def linear_train(x2d, lin, relu=False, weight_nhwc_from=None):
@@ -498,18 +532,39 @@ class _BottleneckFn(torch.autograd.Function):
         p3 = prepared_conv(block.conv3, block.bn3, use_bn)
         s1, _ = _stride_pad(block.conv1)
         s2, _ = _stride_pad(block.conv2)
+        # cfg.TRAIN.CONV_BF16, per convolution (conv1, conv2, conv3, projection): a trainable filter, or a gradient passes through
+        need = ctx.needs_input_grad
+        g1 = need[0] or need[3]
+        g2 = g1 or need[4]
+        g3 = g2 or need[5]
         if block.downsample is not None:
             pd = prepared_conv(block.downsample[0], block.downsample[1], True)
             sd, _ = _stride_pad(block.downsample[0])
-            identity = ops.conv2d_nhwc(x, pd[0], pd[1], pd[2], None, stride=sd, pad=0, relu=False)
+            bfd = conv_bf16_train_wanted(pd[0], sd, 0, need[0] or need[6])
+            if bfd:
+                identity = _conv_fwd_bf16(x, pd, block.downsample[0], None, sd, 0, False)
+            else:
+                identity = ops.conv2d_nhwc(x, pd[0], pd[1], pd[2], None, stride=sd, pad=0, relu=False)
         else:
-            pd, sd, identity = None, 1, x
-        o1 = ops.conv2d_nhwc(x, p1[0], p1[1], p1[2], None, stride=s1, pad=0, relu=True)
-        # the 3x3 layer with its cached Winograd-transformed filter when its tuned plan reads one (re-derived only when the
-        # weights change, i.e. once per optimizer step instead of inside every call)
-        u2 = _winograd_filter(block.conv2, p2[0], tuple(o1.shape[:3]), s2, 1)
-        o2 = ops.conv2d_nhwc(o1, p2[0], p2[1], p2[2], None, stride=s2, pad=1, relu=True, w_winograd=u2)
-        out = ops.conv2d_nhwc(o2, p3[0], p3[1], p3[2], identity, stride=1, pad=0, relu=True)
+            pd, sd, identity, bfd = None, 1, x, False
+        bf = (conv_bf16_train_wanted(p1[0], s1, 0, g1), conv_bf16_train_wanted(p2[0], s2, 1, g2),
+              conv_bf16_train_wanted(p3[0], 1, 0, g3), bfd)
+        if bf[0]:
+            o1 = _conv_fwd_bf16(x, p1, block.conv1, None, s1, 0, True)
+        else:
+            o1 = ops.conv2d_nhwc(x, p1[0], p1[1], p1[2], None, stride=s1, pad=0, relu=True)
+        if bf[1]:
+            o2 = _conv_fwd_bf16(o1, p2, block.conv2, None, s2, 1, True)
+        else:
+            # the 3x3 layer with its cached Winograd-transformed filter when its tuned plan reads one (re-derived only when the
+            # weights change, i.e. once per optimizer step instead of inside every call)
+            u2 = _winograd_filter(block.conv2, p2[0], tuple(o1.shape[:3]), s2, 1)
+            o2 = ops.conv2d_nhwc(o1, p2[0], p2[1], p2[2], None, stride=s2, pad=1, relu=True, w_winograd=u2)
+        if bf[2]:
+            out = _conv_fwd_bf16(o2, p3, block.conv3, identity, 1, 0, True)
+        else:
+            out = ops.conv2d_nhwc(o2, p3[0], p3[1], p3[2], identity, stride=1, pad=0, relu=True)
+        ctx.bf16 = bf
         ctx.block = block
         ctx.meta = (p1, p2, p3, pd, s1, s2, sd)
         ctx.save_for_backward(x, o1, o2, out)
@@ -522,38 +577,52 @@ class _BottleneckFn(torch.autograd.Function):
         p1, p2, p3, pd, s1, s2, sd = ctx.meta
         need_w = [w.requires_grad for w in (blk.conv1.weight, blk.conv2.weight, blk.conv3.weight)]
 
-        def wg(inp, dz, conv, r, stride, pad):
-            return _wgrad(inp, dz, r, r, stride, pad, conv.weight)[0]
+        bf = ctx.bf16     # (conv1, conv2, conv3, projection) run with bf16 operands: the forward's answer holds for the gradients
+
+        def wg(inp, dz, conv, r, stride, pad, bf16=False):
+            return _wgrad(inp, dz, r, r, stride, pad, conv.weight, bf16=bf16)[0]
 
         dz3, d_id = ops.act_bwd(dy.contiguous(), out, p3[1], relu=True, want_res=True)
-        dw3 = wg(o2, dz3, blk.conv3, 1, 1, 0) if need_w[2] else None
+        dw3 = wg(o2, dz3, blk.conv3, 1, 1, 0, bf[2]) if need_w[2] else None
         # the ReLU / folded-BatchNorm backward of conv2 (conv1) is applied by the data-gradient launch of conv3 (conv2) as it
         # stores its result (frcnn_conv2d_bwd_data_act): no separate pass over d_o2 / d_o1
-        w3_t = _transposed_filter(blk.conv3, p3[0])
-        w2_t = _transposed_filter(blk.conv2, p2[0])
-        u2_t = _dgrad_winograd(blk.conv2, w2_t, tuple(o1.shape), s2, 1)
-        if FUSE_ACT_BWD:
-            dz2 = ops.conv2d_bwd_data(dz3, w3_t, tuple(o2.shape), act_y=o2, act_scale=p2[1])
+        if bf[2]:
+            dz2 = _bwd_data_bf16(dz3, blk.conv3, p3[0], tuple(o2.shape), act_y=o2, act_scale=p2[1])
         else:
-            dz2, _ = ops.act_bwd(ops.conv2d_bwd_data(dz3, w3_t, tuple(o2.shape)), o2, p2[1], relu=True)
-        dw2 = wg(o1, dz2, blk.conv2, 3, s2, 1) if need_w[1] else None
-        if FUSE_ACT_BWD:
-            dz1 = ops.conv2d_bwd_data(dz2, w2_t, tuple(o1.shape), stride=s2, pad=1, w_winograd=u2_t, act_y=o1, act_scale=p1[1])
+            w3_t = _transposed_filter(blk.conv3, p3[0])
+            if FUSE_ACT_BWD:
+                dz2 = ops.conv2d_bwd_data(dz3, w3_t, tuple(o2.shape), act_y=o2, act_scale=p2[1])
+            else:
+                dz2, _ = ops.act_bwd(ops.conv2d_bwd_data(dz3, w3_t, tuple(o2.shape)), o2, p2[1], relu=True)
+        dw2 = wg(o1, dz2, blk.conv2, 3, s2, 1, bf[1]) if need_w[1] else None
+        if bf[1]:
+            dz1 = _bwd_data_bf16(dz2, blk.conv2, p2[0], tuple(o1.shape), stride=s2, pad=1, act_y=o1, act_scale=p1[1])
         else:
-            dz1, _ = ops.act_bwd(ops.conv2d_bwd_data(dz2, w2_t, tuple(o1.shape), stride=s2, pad=1, w_winograd=u2_t), o1, p1[1],
-                                 relu=True)
-        dw1 = wg(x, dz1, blk.conv1, 1, s1, 0) if need_w[0] else None
+            w2_t = _transposed_filter(blk.conv2, p2[0])
+            u2_t = _dgrad_winograd(blk.conv2, w2_t, tuple(o1.shape), s2, 1)
+            if FUSE_ACT_BWD:
+                dz1 = ops.conv2d_bwd_data(dz2, w2_t, tuple(o1.shape), stride=s2, pad=1, w_winograd=u2_t, act_y=o1, act_scale=p1[1])
+            else:
+                dz1, _ = ops.act_bwd(ops.conv2d_bwd_data(dz2, w2_t, tuple(o1.shape), stride=s2, pad=1, w_winograd=u2_t), o1, p1[1],
+                                     relu=True)
+        dw1 = wg(x, dz1, blk.conv1, 1, s1, 0, bf[0]) if need_w[0] else None
         dwd = None
         dx = None
+
+        def dgrad(dz, conv, prepared, stride, add, bf16):
+            if bf16:
+                return _bwd_data_bf16(dz, conv, prepared[0], tuple(x.shape), stride=stride, add=add)
+            return ops.conv2d_bwd_data(dz, _transposed_filter(conv, prepared[0]), tuple(x.shape), stride=stride, add=add)
+
         if pd is not None:
             dzd, _ = ops.act_bwd(d_id, None, pd[1], relu=False)
             if blk.downsample[0].weight.requires_grad:
-                dwd = wg(x, dzd, blk.downsample[0], 1, sd, 0)
+                dwd = wg(x, dzd, blk.downsample[0], 1, sd, 0, bf[3])
             if ctx.needs_input_grad[0]:
-                dx = ops.conv2d_bwd_data(dzd, _transposed_filter(blk.downsample[0], pd[0]), tuple(x.shape), stride=sd)
-                dx = ops.conv2d_bwd_data(dz1, _transposed_filter(blk.conv1, p1[0]), tuple(x.shape), stride=s1, add=dx)
+                dx = dgrad(dzd, blk.downsample[0], pd, sd, None, bf[3])
+                dx = dgrad(dz1, blk.conv1, p1, s1, dx, bf[0])
         elif ctx.needs_input_grad[0]:
-            dx = ops.conv2d_bwd_data(dz1, _transposed_filter(blk.conv1, p1[0]), tuple(x.shape), stride=s1, add=d_id)
+            dx = dgrad(dz1, blk.conv1, p1, s1, d_id, bf[0])
         grads = [dw1, dw2, dw3]     # parameter-layout gradients, or None when they were accumulated on the side stream
         if pd is not None:
             grads.append(dwd)

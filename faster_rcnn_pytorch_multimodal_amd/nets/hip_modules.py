@@ -168,6 +168,31 @@ def conv_bf16_eligible(c, k, r, s, stride, pad, strided_out=False):
     return (c > 0 and c % 32 == 0 and k >= 1 and r >= 1 and s >= 1 and stride >= 1 and pad >= 0 and not strided_out)
 
 
+def conv_bf16_train_eligible(c, k, r, s, stride, pad, has_gradient=True):
+    """THE rule of cfg.TRAIN.CONV_BF16 for one convolution of a ``_BottleneckFn`` / ``_ConvFn`` (``conv_bn_act_train``) node:
+    it has a trainable filter or a gradient passes through it (``has_gradient``), and C % 32 == 0 and K % 32 == 0 - then its
+    forward, its data gradient and its filter gradient all multiply bf16-rounded operands.  A convolution is eligible as a
+    whole or not at all; the one exception inside an eligible convolution is the strided 1x1 DATA gradient, which writes a
+    scattered output the bf16 kernel does not have and stays fp32 (``conv_bf16_train_dgrad_fp32``).  Everything else - the
+    stem, the RPN's patch convolutions, the fused heads, ``linear_train``, the MobileNet and VGG16 nodes, any C or K that is
+    no multiple of 32 - never asks.  No per-shape exclusions (profiles/conv_bf16_train.md)."""
+    return bool(has_gradient and c > 0 and c % 32 == 0 and k > 0 and k % 32 == 0 and r >= 1 and s >= 1 and stride >= 1 and pad >= 0)
+
+
+def conv_bf16_train_dgrad_fp32(r, s, stride):
+    """The stated exception of ``conv_bf16_train_eligible``: the strided 1x1 data gradient stays fp32."""
+    return stride > 1 and r == 1 and s == 1
+
+
+def conv_bf16_train_wanted(w_krsc, stride, pad, has_gradient):
+    """cfg.TRAIN.CONV_BF16, a TRAIN-mode forward and an eligible convolution (``conv_bf16_train_eligible``).  Asked once, in the
+    node's forward; its backward follows that answer."""
+    if not cfg.TRAIN.get('CONV_BF16', False) or _NET_MODE != 'TRAIN':
+        return False
+    k, r, s, c = w_krsc.shape
+    return conv_bf16_train_eligible(c, k, r, s, stride, pad, has_gradient)
+
+
 def conv_bf16_wanted(x, w_krsc, stride, pad):
     """cfg.TEST.CONV_BF16, a TEST-mode forward, no gradient wanted and an eligible layer."""
     if not cfg.TEST.get('CONV_BF16', False) or _NET_MODE != 'TEST' or (torch.is_grad_enabled() and x.requires_grad):

@@ -523,6 +523,114 @@ def conv2d_bwd_weight_acc(x, dy, r, s, grad_w, grad_b=None, stride=1, pad=0):
                "frcnn_conv2d_bwd_weight_acc")
 
 
+def _packed_bf16(who, name, t, shape):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _hip.HipError("%s must be a tensor on the MI355X (got %s); this package has no CPU path"
+                            % (name, getattr(t, "device", type(t))))
+    if t.dtype != torch.int16 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _hip.HipError("%s: %s must be a contiguous %s int16 tensor of bf16 words (conv2d_pack_bf16), got %s %s"
+                            % (who, name, tuple(shape), t.dtype, tuple(t.shape)))
+
+
+def conv2d_bwd_data_bf16(dy, w_t_bf16, x_shape, stride=1, pad=0, add=None, act_y=None, act_scale=None, out=None, ws=None):
+    """dx (n,h,w,c) = act_bwd(conv_transpose(bf16(dy), w) [+ add]) with bf16 products and fp32 accumulation  -
+    frcnn_conv2d_bwd_data_bf16: what ``conv2d_bwd_data`` computes, ``add`` / ``act_y`` / ``act_scale`` included, for the stride-1
+    form and the zero-inserted strided r x s form.  ``w_t_bf16`` = conv2d_pack_bf16(conv2d_transpose_filter(w)), (c,r,s,k);
+    needs k % 32 == 0.  The strided 1x1 form (scattered output) has no bf16 form and raises.  ``out`` / ``ws`` (tests): the result /
+    workspace tensor to use."""
+    lib = _hip.load()
+    who = "conv2d_bwd_data_bf16"
+    _dev_f32(dy, "dy")
+    n, h, w, c = [int(v) for v in x_shape]
+    if dy.dim() != 4 or not isinstance(w_t_bf16, torch.Tensor) or w_t_bf16.dim() != 4:
+        raise _hip.HipError("%s: dy must be (n,ho,wo,k) and w_t_bf16 (c,r,s,k)" % who)
+    _, r, s, k = w_t_bf16.shape
+    _packed_bf16(who, "w_t_bf16", w_t_bf16, (c, r, s, dy.shape[-1]))
+    stride, pad = int(stride), int(pad)
+    if k % 32 != 0 or c % 4 != 0:
+        raise _hip.HipError("%s: needs k %% 32 == 0 and c %% 4 == 0, got k = %d, c = %d" % (who, k, c))
+    if stride > 1 and r == 1 and s == 1:
+        raise _hip.HipError("%s: the strided 1x1 data gradient (scattered output) has no bf16 form" % who)
+    if stride < 1 or pad < 0 or h + 2 * pad < r or w + 2 * pad < s or tuple(dy.shape[:3]) != (n,) + conv_out_hw(h, w, r, s, stride, pad):
+        raise _hip.HipError("%s: dy shape %s does not match the forward output" % (who, tuple(dy.shape)))
+    for nm, t in (("add", add), ("act_y", act_y)):
+        if t is not None:
+            _dev_f32(t, nm)
+            if tuple(t.shape) != (n, h, w, c):
+                raise _hip.HipError("%s: %s shape %s != x shape %s" % (who, nm, tuple(t.shape), (n, h, w, c)))
+    if act_scale is not None:
+        _dev_f32(act_scale, "act_scale")
+        if act_y is None or act_scale.numel() != c:
+            raise _hip.HipError("%s: act_scale needs act_y and %d elements" % (who, c))
+    if out is None:
+        dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dy.device)
+    else:
+        dx = out
+        _dev_f32(dx, "out")
+        if tuple(dx.shape) != (n, h, w, c):
+            raise _hip.HipError("%s: out has shape %s, expected %s" % (who, tuple(dx.shape), (n, h, w, c)))
+    if FLOPS is not None:
+        _log_flops('dgrad', 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * k * r * s * c)
+    ws_bytes = lib.frcnn_conv2d_bwd_data_bf16_ws_bytes(n, h, w, c, k, r, s, stride, pad)
+    if ws is None:
+        ws = _workspace(ws_bytes, dy.device) if ws_bytes else None
+    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < ws_bytes:
+        raise _hip.HipError("%s: ws must be a contiguous device tensor of at least %d bytes" % (who, ws_bytes))
+    _hip.check(lib.frcnn_conv2d_bwd_data_bf16(_ptr(dy), _ptr(w_t_bf16), _ptr(add), _ptr(act_y), _ptr(act_scale), _ptr(dx), n, h, w, c,
+                                              k, r, s, stride, pad, _ptr(ws), ws_bytes, _stream()), "frcnn_conv2d_bwd_data_bf16")
+    return dx
+
+
+def conv2d_bwd_weight_bf16_ws_bytes(x_shape, k, r, s, stride=1, pad=0, splits=0):
+    """Workspace bytes of ``conv2d_bwd_weight_bf16`` / ``conv2d_bwd_weight_acc_bf16`` for this shape and split count."""
+    n, h, w, c = [int(v) for v in x_shape]
+    return int(_hip.load().frcnn_conv2d_bwd_weight_bf16_ws_bytes(n, h, w, c, int(k), int(r), int(s), int(stride), int(pad), int(splits)))
+
+
+def _wgrad_bf16_ws(device, n, h, w, c, k, r, s, stride, pad, splits, ws):
+    splits = int(splits)
+    if splits < 0:
+        raise _hip.HipError("conv2d_bwd_weight_bf16: splits must be >= 0 (0 = the library's choice), got %d" % splits)
+    ws_bytes = conv2d_bwd_weight_bf16_ws_bytes((n, h, w, c), k, r, s, stride, pad, splits)
+    if ws is None:
+        ws = _workspace(ws_bytes, device) if ws_bytes else None
+    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < ws_bytes:
+        raise _hip.HipError("conv2d_bwd_weight_bf16: ws must be a contiguous device tensor of at least %d bytes" % ws_bytes)
+    return splits, ws, ws_bytes
+
+
+def conv2d_bwd_weight_bf16(x, dy, r, s, stride=1, pad=0, want_bias=False, splits=0, out=None, ws=None):
+    """(dw (K,R,S,C), db (K,) or None): dw = sum over pixels of bf16(dy) * bf16(patch(x)), fp32 accumulation
+    (frcnn_conv2d_bwd_weight_bf16); db in fp32.  ``splits``: pixel ranges whose fp32 partial sums are added in order (0 = the
+    library's choice; clamped to the number of 32-pixel steps); ``out`` / ``ws`` (tests): the result / workspace tensor to use."""
+    lib = _hip.load()
+    n, h, w, c, k, _ = _wgrad_operands("conv2d_bwd_weight_bf16", x, dy, r, s, stride, pad)
+    if out is None:
+        out = torch.empty((k, r, s, c), dtype=torch.float32, device=x.device)
+    else:
+        _dev_f32(out, "out")
+        if tuple(out.shape) != (k, r, s, c):
+            raise _hip.HipError("conv2d_bwd_weight_bf16: out has shape %s, expected %s" % (tuple(out.shape), (k, r, s, c)))
+    db = torch.empty((k,), dtype=torch.float32, device=x.device) if want_bias else None
+    splits, ws, ws_bytes = _wgrad_bf16_ws(x.device, n, h, w, c, k, r, s, stride, pad, splits, ws)
+    _hip.check(lib.frcnn_conv2d_bwd_weight_bf16(_ptr(x), _ptr(dy), _ptr(out), _ptr(db), n, h, w, c, k, r, s, stride, pad, splits,
+                                                _ptr(ws), ws_bytes, _stream()), "frcnn_conv2d_bwd_weight_bf16")
+    return out, db
+
+
+def conv2d_bwd_weight_acc_bf16(x, dy, r, s, grad_w, grad_b=None, stride=1, pad=0, splits=0, ws=None):
+    """grad_w (K, C_real, R, S) += the bf16-operand filter gradient, grad_b (K,) += the fp32 bias gradient, in place
+    (frcnn_conv2d_bwd_weight_acc_bf16); ``splits`` / ``ws`` as for ``conv2d_bwd_weight_bf16``."""
+    lib = _hip.load()
+    n, h, w, c, k, c_real = _wgrad_operands("conv2d_bwd_weight_acc_bf16", x, dy, r, s, stride, pad, grad_w)
+    if grad_b is not None:
+        _dev_f32(grad_b, "grad_b")
+    splits, ws, ws_bytes = _wgrad_bf16_ws(x.device, n, h, w, c, k, r, s, stride, pad, splits, ws)
+    _hip.check(lib.frcnn_conv2d_bwd_weight_acc_bf16(_ptr(x), _ptr(dy), _ptr(grad_w), c_real, _ptr(grad_b), n, h, w, c, k, r, s,
+                                                    stride, pad, splits, _ptr(ws), ws_bytes, _stream()),
+               "frcnn_conv2d_bwd_weight_acc_bf16")
+
+
 WGRAD_MAX_GROUPS = 24
 
 

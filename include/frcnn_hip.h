@@ -129,6 +129,29 @@ int frcnn_conv2d_bwd_weight_acc_grouped(const float* const* x, const float* cons
                                         int c_real, int n, int h, int w, int c, int k, int r, int s, int stride, int pad,
                                         void* ws, size_t ws_bytes, void* stream);
 
+/* bf16-operand gradients of a convolution (cfg.TRAIN.CONV_BF16; not in the reference): both operands of each product are rounded
+ * to bf16 (nearest even) and multiplied on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; every tensor in memory stays fp32.
+ *   frcnn_conv2d_bwd_data_bf16: dx = act_bwd(conv_transpose(bf16(dy), w_bf16) [+ add]) - what frcnn_conv2d_bwd_data_act computes, for
+ *     the stride-1 form and the zero-inserted strided r x s form (the strided 1x1 form stays fp32: FRCNN_ERR_ARG).  w_crsk_flipped_bf16 =
+ *     frcnn_conv2d_pack_bf16 of frcnn_conv2d_transpose_filter's result; needs k % 32 == 0.  act_y / act_scale are applied by an
+ *     frcnn_act_bwd pass over dx behind the GEMM.  ws: frcnn_conv2d_bwd_data_bf16_ws_bytes.
+ *   frcnn_conv2d_bwd_weight_bf16: dw (k,r,s,c), overwritten = sum over pixels of bf16(dy) * bf16(patch(x)) [db: fp32 column sums of dy].
+ *   frcnn_conv2d_bwd_weight_acc_bf16: the same added into the parameter's gradient (k, c_real, r, s) [grad_b].
+ *     splits: pixel ranges summed into fp32 slabs that are added in range order (0 = the library's choice; clamped to the number
+ *     of 32-pixel steps; a given count beyond 65535 or beyond 256 MB of slabs is FRCNN_ERR_ARG): the result is a fixed function
+ *     of the operands and the split count.  No counters, no atomics.
+ *     ws: frcnn_conv2d_bwd_weight_bf16_ws_bytes with the same `splits` (covers both forms and the bias gradient). */
+size_t frcnn_conv2d_bwd_data_bf16_ws_bytes(int n, int h, int w, int c, int k, int r, int s, int stride, int pad);
+int frcnn_conv2d_bwd_data_bf16(const float* dy, const void* w_crsk_flipped_bf16, const float* add, const float* act_y,
+                               const float* act_scale, float* dx, int n, int h, int w, int c, int k, int r, int s, int stride,
+                               int pad, void* ws, size_t ws_bytes, void* stream);
+size_t frcnn_conv2d_bwd_weight_bf16_ws_bytes(int n, int h, int w, int c, int k, int r, int s, int stride, int pad, int splits);
+int frcnn_conv2d_bwd_weight_bf16(const float* x, const float* dy, float* dw, float* db, int n, int h, int w, int c, int k, int r,
+                                 int s, int stride, int pad, int splits, void* ws, size_t ws_bytes, void* stream);
+int frcnn_conv2d_bwd_weight_acc_bf16(const float* x, const float* dy, float* grad_w, int c_real, float* grad_b, int n, int h,
+                                     int w, int c, int k, int r, int s, int stride, int pad, int splits, void* ws, size_t ws_bytes,
+                                     void* stream);
+
 /* Tuning / test hook: force the workgroup tile to (64*tm) x (64*tn) output pixels x channels for all
  * following frcnn_conv2d_fwd calls of this process; (tm,tn) in {(4,2),(2,4)} (8 waves, one workgroup per
  * CU), {(2,2),(2,1),(1,2),(1,1)} (4 waves); (0,0) restores the automatic choice. */
