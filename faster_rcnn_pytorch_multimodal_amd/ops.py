@@ -63,6 +63,27 @@ def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _given_workspace(who, ws, ws_bytes, device):
+    """The workspace operand of a call that needs ``ws_bytes`` (its ``*_ws_bytes`` query): a fresh one, or the caller's ``ws``
+    (tests: a view between guard bands) after checking that it is a contiguous device tensor of at least that many bytes."""
+    ws_bytes = int(ws_bytes)
+    if ws is None:
+        return _workspace(ws_bytes, device) if ws_bytes else None
+    if not isinstance(ws, torch.Tensor) or not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < ws_bytes:
+        raise _hip.HipError("%s: ws must be a contiguous device tensor of at least %d bytes" % (who, ws_bytes))
+    return ws
+
+
+def _given_output(who, out, shape, device, name="out"):
+    """The result tensor of a call: a fresh one, or the caller's ``out`` (contiguous float32 on the device, of ``shape``)."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    _dev_f32(out, name)
+    if tuple(out.shape) != tuple(shape):
+        raise _hip.HipError("%s: %s has shape %s, expected %s" % (who, name, tuple(out.shape), tuple(shape)))
+    return out
+
+
 # what set_conv_autotune(True) means: 1 = every candidate plan is timed alone on an idle chip, 2 = under load (four launches
 # of the candidate in flight on four streams: ranked by throughput, the objective of the four-frames-in-flight schedule)
 AUTOTUNE_LEVEL = int(os.environ.get('FRCNN_AUTOTUNE_LEVEL', '2'))
@@ -159,9 +180,10 @@ def conv_out_hw(h, w, r, s, stride, pad):
 
 
 def conv2d_nhwc(x, w_krsc, scale=None, shift=None, residual=None, stride=1, pad=0, relu=False, split_k=0, out=None,
-                w_winograd=None):
+                w_winograd=None, ws=None):
     """y = act(conv(x, w) * scale + shift + residual)  —  frcnn_conv2d_fwd (frcnn_conv2d_fwd_pre when the caller supplies
-    the Winograd-transformed filter of a 3x3 / stride 1 / pad 1 layer, see ``winograd_filter``)."""
+    the Winograd-transformed filter of a 3x3 / stride 1 / pad 1 layer, see ``winograd_filter``).  ``ws`` (tests): the
+    workspace tensor to use, at least frcnn_conv2d_fwd_ws_bytes of it."""
     lib = _hip.load()
     _dev_f32(x, "x"); _dev_f32(w_krsc, "w")
     n, h, w, c = x.shape
@@ -185,7 +207,7 @@ def conv2d_nhwc(x, w_krsc, scale=None, shift=None, residual=None, stride=1, pad=
         if tuple(residual.shape) != (n, ho, wo, k):
             raise _hip.HipError("conv2d_nhwc: residual shape %s != output shape %s" % (tuple(residual.shape), (n, ho, wo, k)))
     ws_bytes = lib.frcnn_conv2d_fwd_ws_bytes(n, h, w, c, k, r, s, stride, pad, split_k)
-    ws = _workspace(ws_bytes, x.device) if ws_bytes else None
+    ws = _given_workspace("conv2d_nhwc", ws, ws_bytes, x.device)
     if w_winograd is not None:
         _dev_f32(w_winograd, "w_winograd")
         if tuple(w_winograd.shape) != (16, k, c):
@@ -350,11 +372,11 @@ def dgrad_winograd_wanted(x_shape, k, r, s, stride, pad):
     return winograd_filter_wanted(n, ho, wo, k, c, r, s, 1, 1)
 
 
-def conv2d_bwd_data(dy, w_t, x_shape, stride=1, pad=0, add=None, w_winograd=None, act_y=None, act_scale=None):
+def conv2d_bwd_data(dy, w_t, x_shape, stride=1, pad=0, add=None, w_winograd=None, act_y=None, act_scale=None, out=None, ws=None):
     """dx (n,h,w,c) = conv_transpose(dy, w) [+ add].  w_t = conv2d_transpose_filter(w); x_shape = forward input shape.
     ``w_winograd`` = winograd_filter(w_t) (16, c, k): frcnn_conv2d_bwd_data_pre.  ``act_y`` (shape of dx) [, ``act_scale``
     (c,)]: the result is masked / scaled like ``act_bwd(dx, act_y, act_scale, relu=True)`` would in a second pass
-    (frcnn_conv2d_bwd_data_act; not for the strided 1x1 form)."""
+    (frcnn_conv2d_bwd_data_act; not for the strided 1x1 form).  ``out`` / ``ws`` (tests): the result / workspace tensor to use."""
     lib = _hip.load()
     _dev_f32(dy, "dy"); _dev_f32(w_t, "w_t")
     n, h, w, c = x_shape
@@ -367,12 +389,12 @@ def conv2d_bwd_data(dy, w_t, x_shape, stride=1, pad=0, add=None, w_winograd=None
         _dev_f32(add, "add")
         if tuple(add.shape) != tuple(x_shape):
             raise _hip.HipError("conv2d_bwd_data: add shape %s != x shape %s" % (tuple(add.shape), tuple(x_shape)))
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    dx = _given_output("conv2d_bwd_data", out, x_shape, dy.device)
     if FLOPS is not None:
         _log_flops('dgrad', 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * k * r * s * c,
                    add is None and dgrad_winograd_wanted(x_shape, k, r, s, stride, pad))
     ws_bytes = lib.frcnn_conv2d_bwd_data_ws_bytes(n, h, w, c, k, r, s, stride, pad)
-    ws = _workspace(ws_bytes, dy.device) if ws_bytes else None
+    ws = _given_workspace("conv2d_bwd_data", ws, ws_bytes, dy.device)
     if act_y is not None:
         _dev_f32(act_y, "act_y")
         if tuple(act_y.shape) != tuple(x_shape):
@@ -491,33 +513,34 @@ def _wgrad_operands(who, x, dy, r, s, stride, pad, grad_w=None):
     return n, h, w, c, k, c_real
 
 
-def _wgrad_scratch(lib, device, n, h, w, c, k, r, s, stride, pad):
+def _wgrad_scratch(who, lib, device, n, h, w, c, k, r, s, stride, pad, ws=None):
     """(workspace, its bytes, tile counters) of one frcnn_conv2d_bwd_weight[_acc] call"""
     ws_bytes = lib.frcnn_conv2d_bwd_weight_ws_bytes(n, h, w, c, k, r, s, stride, pad)
-    ws = _workspace(ws_bytes, device) if ws_bytes else None
+    ws = _given_workspace(who, ws, ws_bytes, device)
     return ws, ws_bytes, _tile_counters(device, lib.frcnn_conv2d_bwd_weight_counters(c, k, r, s))
 
 
-def conv2d_bwd_weight(x, dy, r, s, stride=1, pad=0, want_bias=False):
-    """Returns (dw (K,R,S,C), db (K,) or None)."""
+def conv2d_bwd_weight(x, dy, r, s, stride=1, pad=0, want_bias=False, out=None, out_bias=None, ws=None):
+    """Returns (dw (K,R,S,C), db (K,) or None).  ``out`` / ``out_bias`` / ``ws`` (tests): the dw / db / workspace tensor to use."""
     lib = _hip.load()
     n, h, w, c, k, _ = _wgrad_operands("conv2d_bwd_weight", x, dy, r, s, stride, pad)
-    dw = torch.empty((k, r, s, c), dtype=torch.float32, device=x.device)
-    db = torch.empty((k,), dtype=torch.float32, device=x.device) if want_bias else None
-    ws, ws_bytes, counters = _wgrad_scratch(lib, x.device, n, h, w, c, k, r, s, stride, pad)
+    dw = _given_output("conv2d_bwd_weight", out, (k, r, s, c), x.device)
+    db = _given_output("conv2d_bwd_weight", out_bias, (k,), x.device, "out_bias") if want_bias else None
+    ws, ws_bytes, counters = _wgrad_scratch("conv2d_bwd_weight", lib, x.device, n, h, w, c, k, r, s, stride, pad, ws)
     _hip.check(lib.frcnn_conv2d_bwd_weight(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), n, h, w, c, k, r, s, stride, pad,
                                            _ptr(ws), ws_bytes, counters.data_ptr(), _stream()), "frcnn_conv2d_bwd_weight")
     return dw, db
 
 
-def conv2d_bwd_weight_acc(x, dy, r, s, grad_w, grad_b=None, stride=1, pad=0):
+def conv2d_bwd_weight_acc(x, dy, r, s, grad_w, grad_b=None, stride=1, pad=0, ws=None):
     """grad_w (K, C_real, R, S) [or (K, C_real) with r = s = 1] += filter gradient, grad_b (K,) += bias gradient: the
-    parameter's own gradient buffers, accumulated in place (frcnn_conv2d_bwd_weight_acc)."""
+    parameter's own gradient buffers, accumulated in place (frcnn_conv2d_bwd_weight_acc; the results are ``grad_w`` / ``grad_b``
+    themselves, so there is no ``out``).  ``ws`` (tests): the workspace tensor to use."""
     lib = _hip.load()
     n, h, w, c, k, c_real = _wgrad_operands("conv2d_bwd_weight_acc", x, dy, r, s, stride, pad, grad_w)
     if grad_b is not None:
         _dev_f32(grad_b, "grad_b")
-    ws, ws_bytes, counters = _wgrad_scratch(lib, x.device, n, h, w, c, k, r, s, stride, pad)
+    ws, ws_bytes, counters = _wgrad_scratch("conv2d_bwd_weight_acc", lib, x.device, n, h, w, c, k, r, s, stride, pad, ws)
     _hip.check(lib.frcnn_conv2d_bwd_weight_acc(_ptr(x), _ptr(dy), _ptr(grad_w), c_real, _ptr(grad_b), n, h, w, c, k, r, s,
                                                stride, pad, _ptr(ws), ws_bytes, counters.data_ptr(), _stream()),
                "frcnn_conv2d_bwd_weight_acc")
@@ -562,20 +585,11 @@ def conv2d_bwd_data_bf16(dy, w_t_bf16, x_shape, stride=1, pad=0, add=None, act_y
         _dev_f32(act_scale, "act_scale")
         if act_y is None or act_scale.numel() != c:
             raise _hip.HipError("%s: act_scale needs act_y and %d elements" % (who, c))
-    if out is None:
-        dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dy.device)
-    else:
-        dx = out
-        _dev_f32(dx, "out")
-        if tuple(dx.shape) != (n, h, w, c):
-            raise _hip.HipError("%s: out has shape %s, expected %s" % (who, tuple(dx.shape), (n, h, w, c)))
+    dx = _given_output(who, out, (n, h, w, c), dy.device)
     if FLOPS is not None:
         _log_flops('dgrad', 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * k * r * s * c)
     ws_bytes = lib.frcnn_conv2d_bwd_data_bf16_ws_bytes(n, h, w, c, k, r, s, stride, pad)
-    if ws is None:
-        ws = _workspace(ws_bytes, dy.device) if ws_bytes else None
-    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < ws_bytes:
-        raise _hip.HipError("%s: ws must be a contiguous device tensor of at least %d bytes" % (who, ws_bytes))
+    ws = _given_workspace(who, ws, ws_bytes, dy.device)
     _hip.check(lib.frcnn_conv2d_bwd_data_bf16(_ptr(dy), _ptr(w_t_bf16), _ptr(add), _ptr(act_y), _ptr(act_scale), _ptr(dx), n, h, w, c,
                                               k, r, s, stride, pad, _ptr(ws), ws_bytes, _stream()), "frcnn_conv2d_bwd_data_bf16")
     return dx
@@ -587,16 +601,12 @@ def conv2d_bwd_weight_bf16_ws_bytes(x_shape, k, r, s, stride=1, pad=0, splits=0)
     return int(_hip.load().frcnn_conv2d_bwd_weight_bf16_ws_bytes(n, h, w, c, int(k), int(r), int(s), int(stride), int(pad), int(splits)))
 
 
-def _wgrad_bf16_ws(device, n, h, w, c, k, r, s, stride, pad, splits, ws):
+def _wgrad_bf16_ws(who, device, n, h, w, c, k, r, s, stride, pad, splits, ws):
     splits = int(splits)
     if splits < 0:
-        raise _hip.HipError("conv2d_bwd_weight_bf16: splits must be >= 0 (0 = the library's choice), got %d" % splits)
+        raise _hip.HipError("%s: splits must be >= 0 (0 = the library's choice), got %d" % (who, splits))
     ws_bytes = conv2d_bwd_weight_bf16_ws_bytes((n, h, w, c), k, r, s, stride, pad, splits)
-    if ws is None:
-        ws = _workspace(ws_bytes, device) if ws_bytes else None
-    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < ws_bytes:
-        raise _hip.HipError("conv2d_bwd_weight_bf16: ws must be a contiguous device tensor of at least %d bytes" % ws_bytes)
-    return splits, ws, ws_bytes
+    return splits, _given_workspace(who, ws, ws_bytes, device), ws_bytes
 
 
 def conv2d_bwd_weight_bf16(x, dy, r, s, stride=1, pad=0, want_bias=False, splits=0, out=None, ws=None):
@@ -605,14 +615,9 @@ def conv2d_bwd_weight_bf16(x, dy, r, s, stride=1, pad=0, want_bias=False, splits
     library's choice; clamped to the number of 32-pixel steps); ``out`` / ``ws`` (tests): the result / workspace tensor to use."""
     lib = _hip.load()
     n, h, w, c, k, _ = _wgrad_operands("conv2d_bwd_weight_bf16", x, dy, r, s, stride, pad)
-    if out is None:
-        out = torch.empty((k, r, s, c), dtype=torch.float32, device=x.device)
-    else:
-        _dev_f32(out, "out")
-        if tuple(out.shape) != (k, r, s, c):
-            raise _hip.HipError("conv2d_bwd_weight_bf16: out has shape %s, expected %s" % (tuple(out.shape), (k, r, s, c)))
+    out = _given_output("conv2d_bwd_weight_bf16", out, (k, r, s, c), x.device)
     db = torch.empty((k,), dtype=torch.float32, device=x.device) if want_bias else None
-    splits, ws, ws_bytes = _wgrad_bf16_ws(x.device, n, h, w, c, k, r, s, stride, pad, splits, ws)
+    splits, ws, ws_bytes = _wgrad_bf16_ws("conv2d_bwd_weight_bf16", x.device, n, h, w, c, k, r, s, stride, pad, splits, ws)
     _hip.check(lib.frcnn_conv2d_bwd_weight_bf16(_ptr(x), _ptr(dy), _ptr(out), _ptr(db), n, h, w, c, k, r, s, stride, pad, splits,
                                                 _ptr(ws), ws_bytes, _stream()), "frcnn_conv2d_bwd_weight_bf16")
     return out, db
@@ -625,7 +630,7 @@ def conv2d_bwd_weight_acc_bf16(x, dy, r, s, grad_w, grad_b=None, stride=1, pad=0
     n, h, w, c, k, c_real = _wgrad_operands("conv2d_bwd_weight_acc_bf16", x, dy, r, s, stride, pad, grad_w)
     if grad_b is not None:
         _dev_f32(grad_b, "grad_b")
-    splits, ws, ws_bytes = _wgrad_bf16_ws(x.device, n, h, w, c, k, r, s, stride, pad, splits, ws)
+    splits, ws, ws_bytes = _wgrad_bf16_ws("conv2d_bwd_weight_acc_bf16", x.device, n, h, w, c, k, r, s, stride, pad, splits, ws)
     _hip.check(lib.frcnn_conv2d_bwd_weight_acc_bf16(_ptr(x), _ptr(dy), _ptr(grad_w), c_real, _ptr(grad_b), n, h, w, c, k, r, s,
                                                     stride, pad, splits, _ptr(ws), ws_bytes, _stream()),
                "frcnn_conv2d_bwd_weight_acc_bf16")
@@ -634,9 +639,10 @@ def conv2d_bwd_weight_acc_bf16(x, dy, r, s, grad_w, grad_b=None, stride=1, pad=0
 WGRAD_MAX_GROUPS = 24
 
 
-def conv2d_bwd_weight_acc_grouped(xs, dys, r, s, grads, stride=1, pad=0):
+def conv2d_bwd_weight_acc_grouped(xs, dys, r, s, grads, stride=1, pad=0, ws=None):
     """``grads[g]`` += filter gradient of convolution g for up to WGRAD_MAX_GROUPS convolutions of identical shape
-    (frcnn_conv2d_bwd_weight_acc_grouped): one launch pair, no pixel split, no slab reduction."""
+    (frcnn_conv2d_bwd_weight_acc_grouped): one launch pair, no pixel split, no slab reduction.  ``ws`` (tests): the workspace
+    tensor to use."""
     import ctypes
     lib = _hip.load()
     groups = len(xs)
@@ -653,7 +659,7 @@ def conv2d_bwd_weight_acc_grouped(xs, dys, r, s, grads, stride=1, pad=0):
             raise _hip.HipError("%s: grad_w %s does not fit k=%d c<=%d r=%d s=%d" % (who, tuple(gw.shape), k, c, r, s))
     arr = ctypes.c_void_p * groups
     ws_bytes = lib.frcnn_conv2d_bwd_weight_acc_grouped_ws_bytes(groups, c, k, r, s)
-    ws = _workspace(ws_bytes, xs[0].device)
+    ws = _given_workspace("conv2d_bwd_weight_acc_grouped", ws, ws_bytes, xs[0].device)
     _hip.check(lib.frcnn_conv2d_bwd_weight_acc_grouped(arr(*[t.data_ptr() for t in xs]), arr(*[t.data_ptr() for t in dys]),
                                                        arr(*[t.data_ptr() for t in grads]), groups, c_real, n, h, w, c, k, r, s,
                                                        stride, pad, _ptr(ws), ws_bytes, _stream()),

@@ -14,8 +14,8 @@ it).  The filter operand is conv2d_pack_bf16(conv2d_transpose_filter(w)).
 import pytest
 
 import test_conv_wgrad_bf16 as W
+from guarded_buffers import DEV, guarded, guards_intact
 
-DEV = W.DEV
 NAMES = [n for n in W.SHAPES if n != "batch_1x1s2"]
 _CACHE = {}
 
@@ -76,14 +76,14 @@ def run_device(name, dy, wt, add=None, act_y=None, act_scale=None):
     packed = ops.conv2d_pack_bf16(w_t)
     ws_bytes = int(_hip.load().frcnn_conv2d_bwd_data_bf16_ws_bytes(n, h, w, c, k, r, r, stride, pad))
     ws_floats = max((ws_bytes + 3) // 4, 4)
-    wbuf, ws = W.guarded(ws_floats)
-    obuf, out = W.guarded(n * h * w * c)
+    wbuf, ws = guarded(ws_floats)
+    obuf, out = guarded(n * h * w * c)
     res = ops.conv2d_bwd_data_bf16(dev(dy), packed, (n, h, w, c), stride=stride, pad=pad, add=dev(add), act_y=dev(act_y),
                                    act_scale=dev(act_scale), out=out.view(n, h, w, c), ws=ws)
     torch.cuda.synchronize()
     assert res.data_ptr() == out.data_ptr()
-    assert W.guards_intact(obuf, out.numel()), "%s: wrote outside dx" % name
-    assert W.guards_intact(wbuf, ws_floats), "%s: wrote outside the workspace" % name
+    assert guards_intact(obuf, out.numel()), "%s: wrote outside dx" % name
+    assert guards_intact(wbuf, ws_floats), "%s: wrote outside the workspace" % name
     host = out.cpu().double().view(n, h, w, c)
     assert not torch.isnan(host).any(), "%s: an element of dx was not written" % name
     return host

@@ -17,8 +17,7 @@ wrong, and one real layer3 shape.  Every shape runs with 1, 2 and 3 pixel splits
 """
 import pytest
 
-DEV = "cuda:0"
-GUARD = 64
+from guarded_buffers import DEV, GUARD, guarded, guards_intact
 
 # name -> (n, h, w, c, k, r, stride, pad)
 SHAPES = {
@@ -89,21 +88,7 @@ def reference(name, kind):
     return _CACHE[(name, kind)]
 
 
-# ---- guarded device runs -----------------------------------------------------------------------------------------------------
-def guarded(numel, fill=float("nan")):
-    """(buffer, view of ``numel`` floats between two GUARD-float NaN bands), the view filled with ``fill``."""
-    import torch
-    buf = torch.full((numel + 2 * GUARD,), float("nan"), dtype=torch.float32, device=DEV)
-    view = buf[GUARD:GUARD + numel]
-    view.fill_(fill)
-    return buf, view
-
-
-def guards_intact(buf, numel):
-    import torch
-    return bool(torch.isnan(buf[:GUARD]).all() and torch.isnan(buf[GUARD + numel:]).all())
-
-
+# ---- guarded device runs (guarded / guards_intact: guarded_buffers.py) -----------------------------------------------------------
 def run_device(name, x, dy, splits, before=None, want_bias=False):
     """One guarded launch.  ``before`` None: frcnn_conv2d_bwd_weight_bf16 into a NaN-filled dw (k,r,s,c); else the accumulating
     form into a (k,c,r,s) gradient that holds ``before``.  Returns (result as float64 host tensor, db or None)."""
