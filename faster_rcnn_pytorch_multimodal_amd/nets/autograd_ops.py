@@ -187,8 +187,9 @@ def _wgrad(x, d_conv, r, s, stride, pad, weight=None, bias=None, mapped=None, bf
         _launch_wgrad(weight.grad, [x, d_conv], lambda: ops.conv2d_bwd_weight_acc(
             x, d_conv, r, s, weight.grad, bias.grad if bias is not None else None, stride=stride, pad=pad))
     else:
+        # a frozen sibling of a mapped set (one bias of a fused head, the permuted Linear's bias) keeps .grad None, as under autograd
         _launch_wgrad(mapped[0][0], [x, d_conv],
-                      lambda: [_accumulate(p, g) for (p, _), g in zip(mapped, param_layout_grads())])
+                      lambda: [_accumulate(p, g) for (p, _), g in zip(mapped, param_layout_grads()) if p.requires_grad])
     return [None] * len(mapped)
 
 
