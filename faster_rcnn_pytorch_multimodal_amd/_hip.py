@@ -100,6 +100,10 @@ PROTOTYPES = {
                                              POINTER(c_float), c_float, _P, _P, _P, _P, _P, _P]),
     "frcnn_head_fc_softmax_decode_lidar": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P,
                                                    POINTER(c_float), POINTER(c_float), c_float, _P, _P, _P, _P, _P, _P]),
+    "frcnn_head_wide_softmax_decode": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, _P, POINTER(c_float),
+                                               POINTER(c_float), c_float, _P, _P, _P, _P, _P]),
+    "frcnn_head_wide_softmax_decode_lidar": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, POINTER(c_float),
+                                                     POINTER(c_float), c_float, _P, _P, _P, _P, _P]),
     "frcnn_generate_anchors_3d": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "frcnn_filter_set_variant": (c_int, [c_int]),
     "frcnn_filter_per_class_lidar": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_int, c_int, _P, _P, _P, _P,

@@ -391,12 +391,18 @@ class Network(nn.Module):
         return self.resnet.layer4(pool5_nhwc)
 
     def _tail_kernel(self, x_nhwc, rois):
+        """The detection tail on (R, P, P, C): the fused kernel where it accepts the class count, the GEMM-tiled wide form
+        for more classes (ops.head_uses_wide_form; the wide form takes fc7 itself, every caller here passes P = 1)."""
         key = cfg.NET_TYPE.upper() if cfg.NET_TYPE in ('image', 'lidar') else 'IMAGE'
-        return ops.head_fc_softmax_decode(
-            x_nhwc, self.cls_score_net.weight.detach(), self.cls_score_net.bias.detach(),
-            self.bbox_pred_net.weight.detach(), self.bbox_pred_net.bias.detach(), rois.contiguous(),
-            cfg.TRAIN[key].BBOX_NORMALIZE_STDS, cfg.TRAIN[key].BBOX_NORMALIZE_MEANS, self._frame_scale,
-            roi_anchors_3d=self._predictions.get('roi_anchors_3d') if key == 'LIDAR' else None)
+        anchors = self._predictions.get('roi_anchors_3d') if key == 'LIDAR' else None
+        args = (self.cls_score_net.weight.detach(), self.cls_score_net.bias.detach(),
+                self.bbox_pred_net.weight.detach(), self.bbox_pred_net.bias.detach(), rois.contiguous(),
+                cfg.TRAIN[key].BBOX_NORMALIZE_STDS, cfg.TRAIN[key].BBOX_NORMALIZE_MEANS, self._frame_scale)
+        if ops.head_uses_wide_form(self.cls_score_net.weight.shape[0], 7 if key == 'LIDAR' else 4):
+            r, p, _, c = x_nhwc.shape
+            fc7 = x_nhwc.reshape(r, c) if p == 1 else ops.spatial_mean(x_nhwc)
+            return ops.head_softmax_decode_wide(fc7, *args, roi_anchors_3d=anchors)
+        return ops.head_fc_softmax_decode(x_nhwc, *args, roi_anchors_3d=anchors)
 
     def _head_to_tail(self, pool5):
         """Without FPN: layer4 on the pooled RoIs then ``.mean(3).mean(2)`` -> fc7 (R, 2048).

@@ -1177,6 +1177,52 @@ def head_fc_softmax_decode(x, w_cls, b_cls, w_box, b_box, rois, stds, means, sca
     return {"fc7": fc7, "cls_score": cls_score, "cls_prob": cls_prob, "bbox_pred": bbox_pred, "pred_boxes": pred_boxes}
 
 
+HEAD_FUSED_MAX_OUT = 64          # MAX_OUT of csrc/head.hip: the fused tail keeps a RoI's K + E*K head outputs in LDS
+
+
+def head_uses_wide_form(num_classes, box_elems):
+    """Which form of the detection tail runs a frame: the fused one-workgroup-per-RoI kernel (head_fc_softmax_decode) where it
+    accepts the class count, K * (1 + E) <= 64, i.e. up to 12 classes for image boxes (E = 4) and 8 for LiDAR boxes (E = 7);
+    the GEMM-tiled wide form (head_softmax_decode_wide) for every larger K."""
+    return int(num_classes) * (1 + int(box_elems)) > HEAD_FUSED_MAX_OUT
+
+
+def head_softmax_decode_wide(fc7, w_cls, b_cls, w_box, b_box, rois, stds, means, scale, roi_anchors_3d=None):
+    """fc7 (R,C) -> dict(fc7, cls_score, cls_prob, bbox_pred, pred_boxes) for any class count; ``fc7`` is the input tensor.
+    The two heads as one MFMA GEMM, then softmax and decode (frcnn_head_wide_softmax_decode[_lidar]).  With
+    ``roi_anchors_3d`` (R,7) the boxes are the 7-DoF LiDAR boxes, otherwise 4-DoF image boxes."""
+    lib = _hip.load()
+    for nm, t in (("fc7", fc7), ("w_cls", w_cls), ("b_cls", b_cls), ("w_box", w_box), ("b_box", b_box), ("rois", rois)):
+        _dev_f32(t, nm)
+    if fc7.dim() != 2:
+        raise _hip.HipError("head_softmax_decode_wide: fc7 must be (R, C)")
+    r, c = fc7.shape
+    k = w_cls.shape[0]
+    e = 4 if roi_anchors_3d is None else 7
+    if (w_box.shape[0] != e * k or w_cls.shape[1] != c or w_box.shape[1] != c or b_cls.numel() != k or b_box.numel() != e * k
+            or len(stds) != e or len(means) != e or tuple(rois.shape) != (r, 5)):
+        raise _hip.HipError("head_softmax_decode_wide: inconsistent head weights / rois / normalisation for %d-DoF boxes" % e)
+    dev = fc7.device
+    cls_score = torch.empty((r, k), dtype=torch.float32, device=dev)
+    cls_prob = torch.empty((r, k), dtype=torch.float32, device=dev)
+    bbox_pred = torch.empty((r, e * k), dtype=torch.float32, device=dev)
+    pred_boxes = torch.empty((r, e * k), dtype=torch.float32, device=dev)
+    if e == 4:
+        _hip.check(lib.frcnn_head_wide_softmax_decode(
+            _ptr(fc7), r, c, _ptr(w_cls), _ptr(b_cls), _ptr(w_box), _ptr(b_box), k, _ptr(rois),
+            _hip.float_array(stds), _hip.float_array(means), float(scale), _ptr(cls_score), _ptr(cls_prob),
+            _ptr(bbox_pred), _ptr(pred_boxes), _stream()), "frcnn_head_wide_softmax_decode")
+    else:
+        _dev_f32(roi_anchors_3d, "roi_anchors_3d")
+        if tuple(roi_anchors_3d.shape) != (r, 7):
+            raise _hip.HipError("head_softmax_decode_wide: roi_anchors_3d must be (%d, 7)" % r)
+        _hip.check(lib.frcnn_head_wide_softmax_decode_lidar(
+            _ptr(fc7), r, c, _ptr(w_cls), _ptr(b_cls), _ptr(w_box), _ptr(b_box), k, _ptr(rois), _ptr(roi_anchors_3d),
+            _hip.float_array(stds), _hip.float_array(means), float(scale), _ptr(cls_score), _ptr(cls_prob),
+            _ptr(bbox_pred), _ptr(pred_boxes), _stream()), "frcnn_head_wide_softmax_decode_lidar")
+    return {"fc7": fc7, "cls_score": cls_score, "cls_prob": cls_prob, "bbox_pred": bbox_pred, "pred_boxes": pred_boxes}
+
+
 def generate_anchors_3d(base, height, width, feat_stride):
     """base: DEVICE float32 (T, 9) anchor-type table -> (anchors_3d (H*W*T, 7), anchors_2d (H*W*T, 4))."""
     lib = _hip.load()

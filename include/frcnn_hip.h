@@ -528,6 +528,34 @@ int frcnn_head_fc_softmax_decode_lidar(const float* x, int num_rois, int pooled,
                                        float* cls_score, float* cls_prob, float* bbox_pred, float* pred_boxes,
                                        void* stream);
 
+/* Wide form of the tail, for class counts past the limits above (num_classes * 5 > 64 for image boxes, * 8 > 64 for LiDAR
+ * boxes: PASCAL VOC's 21 of lib/datasets/pascal_voc.py, COCO's 81 of lib/datasets/coco.py, KITTI's full label set).  It
+ * replaces the same reference calls on an fc7 that already exists: cls_score = cls_score_net(fc7), cls_prob =
+ * softmax(cls_score, 1), bbox_pred = bbox_pred_net(fc7) (_region_classification of network.py; module names
+ * lib/nets/imagenet.py:83-86) and pred_boxes = bbox_transform_inv(rois[:,1:5], bbox_pred*stds+means, scale)
+ * (lib/model/bbox_transform.py:75-105; lib/model/test.py:75-79).
+ * fc7 (R,C) is an INPUT (every caller pools to 1x1 before the heads); w_cls (K,C) and w_box (4K,C) are read by their own
+ * addresses, 16-byte aligned like fc7.  The two Linear layers run as one 32 x 32-tiled GEMM on v_mfma_f32_32x32x2_f32 with
+ * the channels split over two workgroups; a second launch of one wave per RoI adds the two halves and the bias and does
+ * the softmax and the decode with the arithmetic of the fused kernel (class-order fp32 sum).  No workspace: cls_prob and
+ * pred_boxes hold the second half's sums between the two launches, so the four outputs must be four distinct buffers.  No
+ * atomics, no host synchronisation; a RoI's outputs depend on that RoI's inputs only.  num_rois >= 1, c % 4 == 0, 2 <= num_classes <= 4096 (small class counts are accepted too), scale > 0;
+ * anything else returns FRCNN_ERR_ARG and launches nothing.
+ * Outputs: cls_score (R,K), cls_prob (R,K), bbox_pred (R,4K) raw, pred_boxes (R,4K). */
+int frcnn_head_wide_softmax_decode(const float* fc7, int num_rois, int c, const float* w_cls, const float* b_cls,
+                                   const float* w_box, const float* b_box, int num_classes, const float* rois,
+                                   const float* stds_host, const float* means_host, float scale, float* cls_score,
+                                   float* cls_prob, float* bbox_pred, float* pred_boxes, void* stream);
+
+/* Wide LiDAR tail: as above with 7-DoF boxes - w_box (7K,C), bbox_pred (R,7K), pred_boxes =
+ * lidar_3d_bbox_transform_inv(rois[:,1:5], roi_anchors_3d, bbox_pred*stds+means, scale)
+ * (lib/model/bbox_transform.py:174-233); roi_anchors_3d (R,7) must not be NULL; stds/means 7 floats. */
+int frcnn_head_wide_softmax_decode_lidar(const float* fc7, int num_rois, int c, const float* w_cls, const float* b_cls,
+                                         const float* w_box, const float* b_box, int num_classes, const float* rois,
+                                         const float* roi_anchors_3d, const float* stds_host, const float* means_host,
+                                         float scale, float* cls_score, float* cls_prob, float* bbox_pred,
+                                         float* pred_boxes, void* stream);
+
 /* filter_and_draw_prep + nms_hstack_torch + the max_dets cut (lib/utils/filter_predictions.py:75-130,
  * 45-72; lib/model/test.py:210-221) for the image detector, all on the device:
  * clamp to [0, frame/scale-1] in place, per class j>=1 keep score > thresh, NMS(nms_thresh) in
