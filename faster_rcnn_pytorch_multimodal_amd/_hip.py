@@ -169,6 +169,10 @@ PROTOTYPES = {
     "frcnn_logit_distort": (c_int, [_P, _P, c_int64, c_int, c_uint32, _P, c_uint32, c_int, _P, _P, _P]),
     "frcnn_bayesian_cross_entropy": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_uint32, _P, c_uint32, c_int, c_float, _P, _P, _P,
                                              _P, _P]),
+    "frcnn_bayesian_cross_entropy_wide": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_uint32, _P, c_uint32, c_int, c_float, _P,
+                                                  _P, _P, _P, _P]),
+    "frcnn_uncertainty_columns": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_int),
+                                          POINTER(c_int), _P, _P]),
     "frcnn_exp": (c_int, [_P, c_int64, _P, _P]),
     "frcnn_bbox_transform": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P]),
     "frcnn_lidar_bbox_transform": (c_int, [_P, c_int, _P, _P, c_int, c_int, _P, _P]),

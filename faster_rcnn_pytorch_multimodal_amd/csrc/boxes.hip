@@ -108,6 +108,44 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
   }
 }
 
+// The uncertainty columns of a frame's detections (nms_hstack_var_torch, filter_predictions.py:23-43, and the column
+// stacking of lib/model/test.py:260-270): out (K, M, D + U) = [dets row | the sources' values of the detection's RoI].
+// A per-class source (the box variances) contributes v[roi, j*w:(j+1)*w] for class j, a shared one v[roi, 0:w].  Rows whose
+// det_roi is outside [0, R) (-1 marks padding) keep their box columns and get +0.0 in the uncertainty columns.
+constexpr int UC_MAX_SOURCES = 8;
+struct UcSources {
+  const float* ptr[UC_MAX_SOURCES];
+  int width[UC_MAX_SOURCES];       // output columns
+  int stride[UC_MAX_SOURCES];      // floats per RoI row of the source
+  int per_class[UC_MAX_SOURCES];
+  int end[UC_MAX_SOURCES];         // first output column after this source
+  int count;
+};
+
+__global__ __launch_bounds__(256) void uncertainty_columns_kernel(const float* __restrict__ dets,
+                                                                 const int* __restrict__ det_roi, UcSources src, int M,
+                                                                 int D, int W, int R, size_t total,
+                                                                 float* __restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / (size_t)W;          // j * M + m
+    const int c = (int)(i - row * (size_t)W);
+    if (c < D) {
+      out[i] = dets[row * (size_t)D + c];
+      continue;
+    }
+    const int roi = det_roi[row];
+    float v = 0.f;
+    if (roi >= 0 && roi < R) {
+      int q = 0;
+      while (q + 1 < src.count && c >= src.end[q]) ++q;
+      const int col = c - (src.end[q] - src.width[q]);
+      const int j = (int)(row / (size_t)M);
+      v = src.ptr[q][(size_t)roi * src.stride[q] + (src.per_class[q] ? j * src.width[q] : 0) + col];
+    }
+    out[i] = v;
+  }
+}
+
 __global__ __launch_bounds__(256) void make_rois_kernel(const float* __restrict__ boxes, const float* __restrict__ scs,
                                                        const int64_t* __restrict__ keep_idx,
                                                        const int* __restrict__ keep_count, int max_keep,
@@ -228,6 +266,32 @@ extern "C" int frcnn_gather_rows(const float* rows, const int64_t* order, const 
   hipLaunchKernelGGL(gather_rows_kernel, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0,
                      static_cast<hipStream_t>(stream_), rows, order, count, max_count, width, rows_out);
   return check_launch("gather_rows_kernel");
+}
+
+extern "C" int frcnn_uncertainty_columns(const float* dets, const int* det_roi, int num_classes, int max_out,
+                                         int det_width, int num_rois, int num_sources, const float* const* sources_host,
+                                         const int* widths_host, const int* per_class_host, float* out, void* stream_) {
+  FRCNN_REQUIRE(dets && det_roi && out && sources_host && widths_host && per_class_host,
+                "uncertainty_columns: null argument");
+  FRCNN_REQUIRE(num_classes > 0 && max_out > 0 && det_width > 0 && num_rois > 0 && num_sources > 0 &&
+                    num_sources <= UC_MAX_SOURCES,
+                "uncertainty_columns: bad shape (1 <= sources <= %d)", UC_MAX_SOURCES);
+  UcSources src{};
+  int w = det_width;
+  for (int q = 0; q < num_sources; ++q) {
+    FRCNN_REQUIRE(sources_host[q] && widths_host[q] > 0, "uncertainty_columns: source %d is null or empty", q);
+    src.ptr[q] = sources_host[q];
+    src.width[q] = widths_host[q];
+    src.per_class[q] = per_class_host[q] ? 1 : 0;
+    src.stride[q] = per_class_host[q] ? widths_host[q] * num_classes : widths_host[q];
+    w += widths_host[q];
+    src.end[q] = w;
+  }
+  src.count = num_sources;
+  const size_t total = (size_t)num_classes * max_out * w;
+  hipLaunchKernelGGL(uncertainty_columns_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream_), dets, det_roi, src, max_out, det_width, w, num_rois, total, out);
+  return check_launch("uncertainty_columns_kernel");
 }
 
 extern "C" int frcnn_make_rois(const float* sorted_boxes, const float* sorted_scores, const int64_t* keep_idx,

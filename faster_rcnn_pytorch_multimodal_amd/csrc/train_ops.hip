@@ -651,6 +651,114 @@ __global__ __launch_bounds__(256) void bayes_ce_kernel(const float* __restrict__
     }
   }
 }
+// The same loss for any class count: one wavefront per RoI, four RoIs per workgroup.  Lane l owns classes l, l + 64, ...
+// (CPL slots, in registers); the draws, z, expf and both gradient sums are lane-parallel.  Every sum keeps
+// bayes_ce_kernel's operand order: the maximum is exact in any order, the expf values go to the wave's LDS row and every
+// lane adds them in class order 0..K-1 (one fp32 chain, broadcast reads), and avg / gs / gv accumulate in sample order.
+// The expressions below are bayes_ce_kernel's, so the two kernels agree wherever both accept K.
+constexpr int BAYES_WIDE_WAVES = 4;
+constexpr int BAYES_WIDE_MAX_CLASSES = 1024;
+
+// Orders this wave's LDS traffic: the row is written and read by one wave only, whose LDS instructions complete in issue
+// order, so no workgroup barrier is needed; the fences keep the compiler from moving accesses across this point.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int CPL>
+__global__ __launch_bounds__(64 * BAYES_WIDE_WAVES) void bayes_ce_wide_kernel(
+    const float* __restrict__ score, const float* __restrict__ var, const float* __restrict__ labels, int N, int K, int S,
+    uint32_t seed, const uint32_t* __restrict__ seed_dev, uint32_t stream, int var_is_log, float grad,
+    float* __restrict__ per_roi, float* __restrict__ dscore, float* __restrict__ dvar) {
+  __shared__ __attribute__((aligned(16))) float s_rows[BAYES_WIDE_WAVES][CPL * 64];
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * BAYES_WIDE_WAVES + (threadIdx.x >> 6);
+  if (n >= N) return;                      // whole waves leave; no workgroup barrier below
+  if (seed_dev) seed += *seed_dev;
+  float* row = s_rows[threadIdx.x >> 6];
+  const int tgt = (int)labels[n];
+  float sc[CPL], sd[CPL], gs[CPL], gv[CPL];
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    const int k = lane + 64 * j;
+    sc[j] = sd[j] = gs[j] = gv[j] = 0.f;
+    if (k < K) {
+      sc[j] = score[(size_t)n * K + k];
+      const float v = var[(size_t)n * K + k];
+      sd[j] = sqrtf(var_is_log ? expf(v) : v);
+    }
+  }
+  const bool want = dscore || dvar;
+  float avg = 0.f;
+  for (int s = 0; s < S; ++s) {
+    float z[CPL], e[CPL];
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const int k = lane + 64 * j;
+      e[j] = z[j] = 0.f;
+      if (k < K) {
+        e[j] = normal01(seed, stream, (uint32_t)(((size_t)s * N + n) * K + k));
+        z[j] = sc[j] + sd[j] * e[j];
+        m = fmaxf(m, z[j]);
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const int k = lane + 64 * j;
+      if (k < K) {
+        z[j] = expf(z[j] - m);
+        row[k] = z[j];
+      }
+    }
+    wave_lds_sync();
+    float den = 0.f;
+    const int k4 = K & ~3;
+    for (int k = 0; k < k4; k += 4) {
+      const float4 q = *reinterpret_cast<const float4*>(row + k);
+      den += q.x; den += q.y; den += q.z; den += q.w;
+    }
+    for (int k = k4; k < K; ++k) den += row[k];
+    const float pt = row[tgt] / den;
+    wave_lds_sync();                       // the next sample overwrites the row
+    avg += pt;
+    if (want) {
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) {
+        const int k = lane + 64 * j;
+        if (k < K) {
+          const float d = pt * ((k == tgt ? 1.f : 0.f) - z[j] / den);
+          gs[j] += d;
+          gv[j] += d * e[j];
+        }
+      }
+    }
+  }
+  avg = avg / (float)S;
+  if (lane == 0) per_roi[n] = -logf(avg);
+  const float c = -grad / ((float)N * (float)S * avg);
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    const int k = lane + 64 * j;
+    if (k < K) {
+      if (dscore) dscore[(size_t)n * K + k] = c * gs[j];
+      if (dvar) dvar[(size_t)n * K + k] = var_is_log ? c * gv[j] * sd[j] * 0.5f : (sd[j] > 0.f ? c * gv[j] / (2.0f * sd[j]) : 0.f);
+    }
+  }
+}
+
+template <int CPL>
+static void launch_bayes_ce_wide(hipStream_t stream, const float* score, const float* var, const float* labels, int N,
+                                 int K, int S, uint32_t seed, const uint32_t* seed_dev, uint32_t stream_id,
+                                 int var_is_log, float grad, float* per_roi, float* dscore, float* dvar) {
+  hipLaunchKernelGGL(bayes_ce_wide_kernel<CPL>, dim3((N + BAYES_WIDE_WAVES - 1) / BAYES_WIDE_WAVES),
+                     dim3(64 * BAYES_WIDE_WAVES), 0, stream, score, var, labels, N, K, S, seed, seed_dev, stream_id,
+                     var_is_log, grad, per_roi, dscore, dvar);
+}
+
 __global__ __launch_bounds__(256) void mean_reduce_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
   __shared__ float red[4];
   float s = 0.f;
@@ -727,6 +835,33 @@ extern "C" int frcnn_bayesian_cross_entropy(const float* cls_score, const float*
   hipLaunchKernelGGL(bayes_ce_kernel, dim3(grid_for((size_t)num_rois)), dim3(256), 0, stream, cls_score, cls_var, labels,
                      num_rois, num_classes, num_samples, seed, seed_dev, stream_id, var_is_log, grad, per_roi, dscore, dvar);
   int rc = check_launch("bayes_ce_kernel");
+  if (rc != FRCNN_OK) return rc;
+  hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(256), 0, stream, per_roi, num_rois, loss);
+  return check_launch("mean_reduce_kernel");
+}
+
+extern "C" int frcnn_bayesian_cross_entropy_wide(const float* cls_score, const float* cls_var, const float* labels,
+                                                 int num_rois, int num_classes, int num_samples, uint32_t seed,
+                                                 const uint32_t* seed_dev, uint32_t stream_id, int var_is_log,
+                                                 float grad, float* loss, float* per_roi, float* dscore, float* dvar,
+                                                 void* stream_) {
+  FRCNN_REQUIRE(cls_score && cls_var && labels && loss && per_roi, "bayesian_cross_entropy_wide: null argument");
+  FRCNN_REQUIRE(num_rois > 0 && num_classes > 1 && num_classes <= BAYES_WIDE_MAX_CLASSES && num_samples > 0 &&
+                    (int64_t)num_rois * num_classes * num_samples < ((int64_t)1 << 32),
+                "bayesian_cross_entropy_wide: bad arguments (2 <= classes <= %d, rois * classes * samples < 2^32)",
+                BAYES_WIDE_MAX_CLASSES);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int cpl = (num_classes + 63) / 64;
+#define FRCNN_BAYES_WIDE(CPL)                                                                                          \
+  launch_bayes_ce_wide<CPL>(stream, cls_score, cls_var, labels, num_rois, num_classes, num_samples, seed, seed_dev,    \
+                            stream_id, var_is_log, grad, per_roi, dscore, dvar)
+  if (cpl <= 1) FRCNN_BAYES_WIDE(1);
+  else if (cpl <= 2) FRCNN_BAYES_WIDE(2);
+  else if (cpl <= 4) FRCNN_BAYES_WIDE(4);
+  else if (cpl <= 8) FRCNN_BAYES_WIDE(8);
+  else FRCNN_BAYES_WIDE(16);
+#undef FRCNN_BAYES_WIDE
+  int rc = check_launch("bayes_ce_wide_kernel");
   if (rc != FRCNN_OK) return rc;
   hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(256), 0, stream, per_roi, num_rois, loss);
   return check_launch("mean_reduce_kernel");

@@ -245,10 +245,20 @@ def classify_test(net, fc7, rois):
     return cls_prob, p['bbox_pred']
 
 
+def append_uncertainty_columns(dets, uncertainties, det_roi):
+    """dets (K, max_out, D) followed by every detection's uncertainty columns in UNCERTAINTY_ORDER, in one launch
+    (``ops.uncertainty_columns``): box variances take the detection's class columns, class terms are shared by all
+    classes.  Equal to ``torch.cat((dets, stack_uncertainty_columns(...)), 2)`` on valid rows; padding rows get +0.0."""
+    sources = [(uncertainties[name].contiguous(), name.endswith('bbox_var')) for name in UNCERTAINTY_ORDER
+               if name in uncertainties]
+    return ops.uncertainty_columns(dets.contiguous(), det_roi.contiguous(), sources)
+
+
 def stack_uncertainty_columns(uncertainties, det_roi, num_classes):
     """Per-detection uncertainty columns in UNCERTAINTY_ORDER (nms_hstack_var_torch, filter_predictions.py:23-43):
     det_roi (K, max_out) int32 RoI row of each detection (-1 = padding) -> (K, max_out, U) float32, zeros on padding.
-    Box variances take the detection's class columns, class terms are shared by all classes."""
+    Box variances take the detection's class columns, class terms are shared by all classes.
+    The host statement of ``append_uncertainty_columns`` (one gather per class and source): the tests compare the two."""
     k, m = det_roi.shape
     idx = det_roi.clamp(min=0).long()
     valid = (det_roi >= 0).unsqueeze(-1).float()
@@ -389,8 +399,11 @@ class _DetLossUcFn(torch.autograd.Function):
                                               lidar=lidar)
         losses = losses.clone()
         if cls_var is not None:
-            ce, dcls, dcvar = ops.bayesian_cross_entropy(cls_score, cls_var, labels, num_ce, seed, STREAM['bayes_ce'],
-                                                         var_is_log=CLS_VAR_IS_LOG, seed_dev=seed_dev)
+            # one thread per RoI up to 16 classes, one wave per RoI above: the same draws, the same bits where both apply
+            bayes_ce = (ops.bayesian_cross_entropy_wide if ops.bayes_ce_uses_wide_form(cls_score.shape[1])
+                        else ops.bayesian_cross_entropy)
+            ce, dcls, dcvar = bayes_ce(cls_score, cls_var, labels, num_ce, seed, STREAM['bayes_ce'],
+                                       var_is_log=CLS_VAR_IS_LOG, seed_dev=seed_dev)
             losses[0] = ce[0]
         ctx.save_for_backward(dcls, dbox, dvar, dcvar)
         return losses

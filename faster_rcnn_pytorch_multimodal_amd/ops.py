@@ -1028,6 +1028,42 @@ def gather_rows(rows, order, count=None):
     return out
 
 
+def uncertainty_columns(dets, det_roi, sources, out=None):
+    """Detections followed by their uncertainty columns in ONE launch (nms_hstack_var_torch, filter_predictions.py:23-43,
+    and the stacking of lib/model/test.py:260-270).  dets (K, M, D) float32, det_roi (K, M) int32 RoI row of each
+    detection (-1 = padding), ``sources`` a sequence of up to 8 ``(tensor, per_class)``: a per-class source is
+    (R, K * w) and class j takes columns [j*w, (j+1)*w) of its RoI's row; a shared source is (R, w) or (R,) and every
+    class takes the whole row.  Returns (K, M, D + U); padding rows keep their box columns and get +0.0 after them."""
+    lib = _hip.load()
+    _dev_f32(dets, "dets")
+    if dets.dim() != 3 or det_roi.dtype != torch.int32 or not det_roi.is_cuda or not det_roi.is_contiguous() or \
+            tuple(det_roi.shape) != tuple(dets.shape[:2]):
+        raise _hip.HipError("uncertainty_columns: dets (K, M, D) float32 and det_roi (K, M) int32, contiguous, on the device")
+    k, m, d = dets.shape
+    if not sources or len(sources) > 8:
+        raise _hip.HipError("uncertainty_columns: 1 to 8 sources, got %d" % len(sources))
+    r = sources[0][0].shape[0]
+    ptrs, widths, kinds = [], [], []
+    for i, (v, per_class) in enumerate(sources):
+        _dev_f32(v, "source %d" % i)
+        cols = v.shape[1] if v.dim() == 2 else 1
+        if v.dim() not in (1, 2) or v.shape[0] != r or (per_class and (v.dim() != 2 or cols % k)):
+            raise _hip.HipError("uncertainty_columns: source %d is %s for %d RoIs and %d classes" % (i, tuple(v.shape), r, k))
+        ptrs.append(v.data_ptr()); widths.append(cols // k if per_class else cols); kinds.append(1 if per_class else 0)
+    w = d + sum(widths)
+    if out is None:
+        out = torch.empty((k, m, w), dtype=torch.float32, device=dets.device)
+    elif tuple(out.shape) != (k, m, w) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise _hip.HipError("uncertainty_columns: out must be a contiguous float32 (%d, %d, %d) device tensor" % (k, m, w))
+    if k * m == 0:
+        return out
+    ns = len(ptrs)
+    _hip.check(lib.frcnn_uncertainty_columns(_ptr(dets), _ptr(det_roi), k, m, d, r, ns, (ctypes.c_void_p * ns)(*ptrs),
+                                             (ctypes.c_int * ns)(*widths), (ctypes.c_int * ns)(*kinds), _ptr(out), _stream()),
+               "frcnn_uncertainty_columns")
+    return out
+
+
 def set_nms_suppress_at_equal(on):
     """IoU == threshold exactly: True (default) suppresses like torchvision 0.4.0's CPU kernel (`>=`), False keeps the box
     like its CUDA kernel (`>`).  Returns the previous setting."""
@@ -1914,20 +1950,50 @@ def exp(x):
 
 def bayesian_cross_entropy(cls_score, cls_var, labels, num_samples, seed, stream_id, grad=1.0, want_grad=True,
                            var_is_log=False, seed_dev=None):
-    """bayesian_cross_entropy (loss_utils.py:149-169).  Returns (loss (1,), dscore, dvar) (gradients scaled by grad)."""
+    """bayesian_cross_entropy (loss_utils.py:149-169).  Returns (loss (1,), dscore, dvar) (gradients scaled by grad).
+    One thread per RoI, at most 16 classes; ``bayesian_cross_entropy_wide`` takes any class count."""
+    return _bayesian_cross_entropy("frcnn_bayesian_cross_entropy", cls_score, cls_var, labels, num_samples, seed, stream_id,
+                                   grad, want_grad, var_is_log, seed_dev)[:3]
+
+
+def _bayesian_cross_entropy(entry, cls_score, cls_var, labels, num_samples, seed, stream_id, grad, want_grad, var_is_log,
+                            seed_dev):
     lib = _hip.load()
     _dev_f32(cls_score, "cls_score"); _dev_f32(cls_var, "cls_var"); _dev_f32(labels, "labels")
     n, k = cls_score.shape
+    if tuple(cls_var.shape) != (n, k) or labels.numel() != n:
+        raise _hip.HipError("%s: score %s, var %s, %d labels" % (entry[6:], tuple(cls_score.shape), tuple(cls_var.shape),
+                                                                 labels.numel()))
     dev = cls_score.device
     loss = torch.empty((1,), dtype=torch.float32, device=dev)
     per_roi = torch.empty((n,), dtype=torch.float32, device=dev)
     dscore = torch.empty_like(cls_score) if want_grad else None
     dvar = torch.empty_like(cls_var) if want_grad else None
-    _hip.check(lib.frcnn_bayesian_cross_entropy(_ptr(cls_score), _ptr(cls_var), _ptr(labels), n, k, int(num_samples),
-                                                int(seed) & 0xFFFFFFFF, _seed_dev(seed_dev), int(stream_id) & 0xFFFFFFFF,
-                                                int(bool(var_is_log)), float(grad), _ptr(loss), _ptr(per_roi), _ptr(dscore), _ptr(dvar), _stream()),
-               "frcnn_bayesian_cross_entropy")
-    return loss, dscore, dvar
+    _hip.check(getattr(lib, entry)(_ptr(cls_score), _ptr(cls_var), _ptr(labels), n, k, int(num_samples),
+                                   int(seed) & 0xFFFFFFFF, _seed_dev(seed_dev), int(stream_id) & 0xFFFFFFFF,
+                                   int(bool(var_is_log)), float(grad), _ptr(loss), _ptr(per_roi), _ptr(dscore), _ptr(dvar),
+                                   _stream()), entry)
+    return loss, dscore, dvar, per_roi
+
+
+BAYES_CE_NARROW_MAX_CLASSES = 16       # KMAX of bayes_ce_kernel (csrc/train_ops.hip)
+BAYES_CE_WIDE_MAX_CLASSES = 1024       # BAYES_WIDE_MAX_CLASSES
+
+
+def bayes_ce_uses_wide_form(num_classes):
+    """The rule nets/uncertainty._DetLossUcFn follows: the one-thread-per-RoI kernel wherever it accepts the class count
+    (every detector that trained before launches the kernel it launched before), the one-wave-per-RoI kernel above."""
+    return int(num_classes) > BAYES_CE_NARROW_MAX_CLASSES
+
+
+def bayesian_cross_entropy_wide(cls_score, cls_var, labels, num_samples, seed, stream_id, grad=1.0, want_grad=True,
+                                var_is_log=False, seed_dev=None, want_per_roi=False):
+    """``bayesian_cross_entropy`` for 2 <= classes <= 1024: one wavefront per RoI, the same draws and the same order of
+    every sum, so both give the same bits where both accept the class count.  ``want_per_roi`` appends the (N,) per-RoI
+    losses the mean is taken over."""
+    out = _bayesian_cross_entropy("frcnn_bayesian_cross_entropy_wide", cls_score, cls_var, labels, num_samples, seed,
+                                  stream_id, grad, want_grad, var_is_log, seed_dev)
+    return out if want_per_roi else out[:3]
 
 
 def bbox_overlaps(boxes, query_boxes):

@@ -6,7 +6,6 @@ boxes to the frame, thresholds, sorts by (score desc, roi index asc), runs NMS a
 optionally applies the ``max_dets`` cut of lib/model/test.py:213-221; a single device->host copy follows.
 """
 import numpy as np
-import torch
 
 from .. import ops
 from ..model.config import cfg
@@ -33,10 +32,9 @@ def filter_device(rois_count, cls_prob, pred_boxes, info, thresh=0.1, max_dets=0
                                    cfg.TEST.NMS_THRESH, max_dets, max_out, roi_count=rois_count, want_rois=want)
     if not want:
         return out
-    from ..nets.uncertainty import stack_uncertainty_columns
+    from ..nets.uncertainty import append_uncertainty_columns
     dets, det_count, det_roi = out
-    cols = stack_uncertainty_columns(uncertainties, det_roi, cls_prob.shape[1])
-    return torch.cat((dets, cols), 2).contiguous(), det_count
+    return append_uncertainty_columns(dets, uncertainties, det_roi), det_count
 
 
 def filter_and_draw_prep(rois, cls_score, pred_boxes, uncertainties, info, num_classes, thresh=0.1, db_type='none'):

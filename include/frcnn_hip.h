@@ -435,6 +435,21 @@ int frcnn_sort_topk_desc(const float* scores, int n, int top_n, int64_t* order_o
 int frcnn_gather_rows(const float* rows, const int64_t* order, const int* count, int max_count, int width,
                       float* rows_out, void* stream);
 
+/* The uncertainty columns of a frame's detections in one launch (version 124): nms_hstack_var_torch,
+ * lib/utils/filter_predictions.py:23-43, plus the column stacking of lib/model/test.py:260-270.
+ *   dets (num_classes, max_out, det_width), det_roi (num_classes, max_out) int32 RoI row of each detection, -1 = padding;
+ *   out (num_classes, max_out, det_width + sum of widths) = [dets row | source 0 | source 1 | ...].
+ * sources_host / widths_host / per_class_host are HOST arrays of num_sources (1..8) entries: a device pointer, the
+ * number of output columns, and the kind.  per_class != 0: the source is (num_rois, num_classes * width) and class j
+ * takes columns [j*width, (j+1)*width) of its RoI's row (the *bbox_var terms); per_class == 0: the source is
+ * (num_rois, width) and every class takes the whole row (entropy, mutual information: width 1; class variances).
+ * Valid rows are copies.  Rows with det_roi outside [0, num_rois) keep their box columns and receive +0.0 in the
+ * uncertainty columns.  The host arrays are read during the call only; no workspace, no host synchronisation, the launch
+ * captures into a hipGraph. */
+int frcnn_uncertainty_columns(const float* dets, const int* det_roi, int num_classes, int max_out, int det_width,
+                              int num_rois, int num_sources, const float* const* sources_host, const int* widths_host,
+                              const int* per_class_host, float* out, void* stream);
+
 /* torchvision.ops.nms at IoU == threshold exactly (proposal_layer.py:46, filter_predictions.py:67-69): on != 0 (default)
  * suppresses the box like torchvision 0.4.0's CPU kernel (`iou >= threshold`), 0 keeps it like its CUDA kernel
  * (`iou > threshold`).  Process-wide, read when frcnn_nms / frcnn_filter_per_class* launch. */
@@ -961,6 +976,16 @@ int frcnn_bayesian_cross_entropy(const float* cls_score, const float* cls_var, c
                                  int num_classes, int num_samples, uint32_t seed, const uint32_t* seed_dev,
                                  uint32_t stream_id, int var_is_log, float grad, float* loss, float* per_roi,
                                  float* dscore, float* dvar, void* stream);
+/* The same loss (loss_utils.py:149-169), arguments and draws for 2 <= num_classes <= 1024 (version 124): one wavefront
+ * per RoI, lane l owning classes l, l + 64, ...  eps[s][n][k] = normal01(seed + *seed_dev, stream_id, (s*N + n)*K + k)
+ * as above.  Every sum keeps the operand order of frcnn_bayesian_cross_entropy (softmax denominator in class order,
+ * avg / gradient sums in sample order), so the result does not depend on the launch geometry and equals the entry above
+ * wherever both accept num_classes.  No atomics, no workspace; dscore / dvar may be NULL; var == 0 with var_is_log == 0
+ * gives dvar = 0.  The host chooses the form (ops.bayes_ce_uses_wide_form: num_classes > 16). */
+int frcnn_bayesian_cross_entropy_wide(const float* cls_score, const float* cls_var, const float* labels, int num_rois,
+                                      int num_classes, int num_samples, uint32_t seed, const uint32_t* seed_dev,
+                                      uint32_t stream_id, int var_is_log, float grad, float* loss, float* per_roi,
+                                      float* dscore, float* dvar, void* stream);
 /* y = exp(x) elementwise (log-variance heads -> variances at test time). */
 int frcnn_exp(const float* x, int64_t elems, float* y, void* stream);
 
