@@ -132,6 +132,9 @@ PROTOTYPES = {
     "frcnn_eval_match_ws_bytes": (c_size_t, [c_int, c_int]),
     "frcnn_eval_match": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_double, c_double,
                                  c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "frcnn_coco_match_ws_bytes": (c_size_t, [c_int] * 4),
+    "frcnn_coco_match": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, _P, c_int64, c_int, _P, c_int, _P, c_int, c_int, _P, _P, _P,
+                                 _P, _P, c_size_t, _P]),
     "frcnn_bn_train_ws_bytes": (c_size_t, [c_int]),
     "frcnn_bn_train_counters": (c_int, [c_int]),
     "frcnn_bn_train_fwd": (c_int, [_P, c_int64, c_int, _P, _P, c_float, c_float, _P, _P, _P, c_int, _P, _P, _P, _P,

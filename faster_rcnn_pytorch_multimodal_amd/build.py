@@ -45,6 +45,7 @@ SOURCES = {
     "image_augment.hip": ["-ffp-contract=off"],
     "image_spatter.hip": ["-ffp-contract=off"],
     "eval_match.hip": ["-ffp-contract=off"],
+    "coco_match.hip": ["-ffp-contract=off"],
     "optim.hip": ["-ffp-contract=off"],
     "nms_rotated.hip": ["-ffp-contract=off"],
 }

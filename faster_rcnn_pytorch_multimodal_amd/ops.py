@@ -11,6 +11,7 @@ import ctypes
 
 import os
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -1617,6 +1618,99 @@ def eval_match(det_boxes, det_rows, det_offsets, gt_boxes, gt_ignore, gt_difficu
                                     _ptr(ovmax_dc), _ptr(dif), _ptr(hit), _ptr(ws), nbytes, _stream()),
                "frcnn_eval_match")
     return code, jmax, ovmax, ovmax_dc, dif, hit
+
+
+# frcnn_coco_match: the kernel's three sizes (include/frcnn_hip.h FRCNN_COCO_*)
+COCO_PAIRS_PER_WG, COCO_LDS_IOUS, COCO_MASK_GT = 4, 1024, 64
+
+
+def coco_match(det, det_offsets, gt, gt_crowd, gt_offsets, iou_thrs, area_rng, out=None, ws=None):
+    """COCO bbox matching of every (image, category) pair in one launch (frcnn_coco_match; the call lib/datasets/coco.py:251-258
+    makes through pycocotools' COCOeval.evaluate, restated in datasets/coco_eval.py).
+    Device tensors: ``det`` (D, 5) float64 [x, y, w, h, area], each pair's detections in descending score order and cut to
+    the largest maxDets; ``gt`` (G, 5) float64 in annotation order; ``gt_crowd`` (G,) uint8 or bool.
+    HOST int32 arrays (numpy or CPU tensors), because the host made them and the checks below read them without a device
+    round trip: ``det_offsets`` / ``gt_offsets`` (P + 1,), ascending inside [0, D] / [0, G]; rows that no pair owns are left alone.  ``iou_thrs`` (T,) and ``area_rng``
+    (A, 2): float64, host or device, used as they are (np.linspace is never recomputed).
+    ``out``: None, or (ious, dt_match, dt_ignore, gt_ignore) device tensors of the shapes below (tests: views between
+    guard bands); ``ws``: None or a workspace of frcnn_coco_match_ws_bytes bytes.
+    Returns ``(ious, iou_offsets, dt_match, dt_ignore, gt_ignore)``: float64 (sum of D_p * G_p,) with pair p's D_p x G_p
+    matrix at the host int64 array ``iou_offsets[p]``, int32 (D, A, T) matched box inside the pair or -1, uint8 (D, A, T),
+    uint8 (G, A).  No host synchronisation."""
+    lib = _hip.load()
+
+    def dev(t, name, dtypes, cols=None):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _hip.HipError("coco_match: %s must be a tensor on the MI355X (got %s); this package has no CPU path"
+                                % (name, getattr(t, "device", type(t))))
+        if t.dtype not in dtypes or not t.is_contiguous():
+            raise _hip.HipError("coco_match: %s must be contiguous %s (got %s)" % (name, dtypes[0], t.dtype))
+        if (t.dim() != 1) if cols is None else (t.dim() != 2 or t.shape[1] != cols):
+            raise _hip.HipError("coco_match: %s must have shape %s, got %s"
+                                % (name, "(n,)" if cols is None else "(n, %d)" % cols, tuple(t.shape)))
+        return t
+
+    def host_offsets(o, name, total):
+        if isinstance(o, torch.Tensor):
+            if o.is_cuda:
+                raise _hip.HipError("coco_match: %s must be a HOST integer array (it is checked before the launch)" % name)
+            o = o.numpy()
+        o = np.asarray(o)
+        if o.dtype.kind not in "iu" or o.ndim != 1 or o.size < 1:
+            raise _hip.HipError("coco_match: %s must be a host integer array of pairs + 1 entries" % name)
+        o = o.astype(np.int64)
+        if o[0] < 0 or o[-1] > total or (np.diff(o) < 0).any():
+            raise _hip.HipError("coco_match: %s must ascend inside [0, %d]" % (name, total))
+        return o
+
+    dev(det, "det", (torch.float64,), 5)
+    dev(gt, "gt", (torch.float64,), 5)
+    device = det.device
+    num_det, num_gt = int(det.shape[0]), int(gt.shape[0])
+    dev(gt_crowd, "gt_crowd", (torch.uint8, torch.bool))
+    if gt_crowd.numel() != num_gt:
+        raise _hip.HipError("coco_match: gt_crowd must have one entry per box")
+    d_off = host_offsets(det_offsets, "det_offsets", num_det)
+    g_off = host_offsets(gt_offsets, "gt_offsets", num_gt)
+    if d_off.size != g_off.size:
+        raise _hip.HipError("coco_match: det_offsets and gt_offsets must both hold pairs + 1 entries (got %d and %d)"
+                            % (d_off.size, g_off.size))
+    num_pairs = d_off.size - 1
+    n_d, n_g = np.diff(d_off), np.diff(g_off)
+    i_off = np.zeros(num_pairs + 1, dtype=np.int64)
+    np.cumsum(n_d * n_g, out=i_off[1:])
+    num_iou = int(i_off[-1])
+    max_gt = int(n_g.max()) if num_pairs else 0
+
+    def small(a, name, shape_ok):
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+        if a.dtype != torch.float64 or not shape_ok(a) or a.numel() == 0:
+            raise _hip.HipError("coco_match: %s must be float64 of shape %s" % (name, "(T,)" if name == "iou_thrs" else "(A, 2)"))
+        return a.contiguous().to(device, non_blocking=True)
+
+    thr = small(iou_thrs, "iou_thrs", lambda a: a.dim() == 1)
+    rng = small(area_rng, "area_rng", lambda a: a.dim() == 2 and a.shape[1] == 2)
+    num_thr, num_area = int(thr.numel()), int(rng.shape[0])
+    shapes = ((num_iou,), (num_det, num_area, num_thr), (num_det, num_area, num_thr), (num_gt, num_area))
+    dtypes = (torch.float64, torch.int32, torch.uint8, torch.uint8)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=device) for s, d in zip(shapes, dtypes))
+    else:
+        if len(out) != 4:
+            raise _hip.HipError("coco_match: out is (ious, dt_match, dt_ignore, gt_ignore)")
+        for t, s, d, name in zip(out, shapes, dtypes, ("ious", "dt_match", "dt_ignore", "gt_ignore")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous():
+                raise _hip.HipError("coco_match: out %s must be a contiguous %s device tensor of shape %s" % (name, d, s))
+    ious, dt_match, dt_ignore, gt_ignore = out
+    up = [torch.from_numpy(o).to(device, non_blocking=True) for o in (d_off.astype(np.int32), g_off.astype(np.int32), i_off)]
+    nbytes = lib.frcnn_coco_match_ws_bytes(num_gt, max_gt, num_area, num_thr)
+    ws = _given_workspace("coco_match", ws, nbytes, device)
+    _hip.check(lib.frcnn_coco_match(_ptr(det), _ptr(up[0]), num_det, _ptr(gt), _ptr(gt_crowd), _ptr(up[1]), num_gt,
+                                    _ptr(up[2]), num_iou, num_pairs, _ptr(thr), num_thr, _ptr(rng), num_area, max_gt,
+                                    _ptr(ious), _ptr(dt_match), _ptr(dt_ignore), _ptr(gt_ignore), _ptr(ws), nbytes,
+                                    _stream()), "frcnn_coco_match")
+    return ious, i_off, dt_match, dt_ignore, gt_ignore
 
 
 # ----------------------------------------------------------------------------------------------

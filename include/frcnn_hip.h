@@ -765,6 +765,41 @@ int frcnn_eval_match(const double* det_boxes, const int* det_rows, const int* de
                      double ovthresh, double ovthresh_dc, int max_gt_per_frame, int* code, int* jmax, double* ovmax,
                      double* ovmax_dc, int* det_difficulty, uint8_t* hit, void* ws, size_t ws_bytes, void* stream);
 
+/* COCO bbox matching of a whole results file: what COCOeval.evaluate() does for every (image, category) pair, the call
+ * lib/datasets/coco.py:251-258 makes through pycocotools, as one launch (csrc/coco_match.hip; the protocol is restated in
+ * datasets/coco_eval.py, parity against pycocotools unpinned).  One wavefront per pair, FRCNN_COCO_PAIRS_PER_WG pairs per
+ * workgroup.  All arrays are device arrays; pair p owns detections det_offsets[p] .. det_offsets[p+1]-1, gt boxes
+ * gt_offsets[p] .. and overlaps iou_offsets[p] .. (num_pairs + 1 entries each, ascending, last = count; iou_offsets is the
+ * running sum of D * G and 64 bits wide).  Ordering is an input, the device never sorts:
+ *   det (num_det, 5) double [x, y, w, h, area], a pair's detections in descending score order, cut to the largest maxDets;
+ *   gt (num_gt, 5) double [x, y, w, h, area] in annotation order, gt_crowd (num_gt) bytes;
+ *   iou_thrs (num_thr) double and area_rng (num_area, 2) double [lo, hi], as numpy made them.
+ * Outputs, per pair:
+ *   ious       D x G doubles, row = detection: iw = min(dx+dw, gx+gw) - max(dx, gx), ih likewise; 0 if iw <= 0 or ih <= 0, else
+ *              iw*ih / (crowd ? dw*dh : dw*dh + gw*gh - iw*ih), each operation rounded once;
+ *   gt_ignore  (num_gt, num_area) bytes: crowd, or area < lo, or area > hi;
+ *   dt_match   (num_det, num_area, num_thr) ints: the matched box's index inside the pair in annotation order, or -1.
+ *              Detections are walked in order; a detection starts from min(thr, 1 - 1e-10), visits the non-ignored boxes
+ *              in annotation order and then, only if none of them matched, the ignored ones; a box that is already matched
+ *              at this (area range, threshold) is skipped unless it is crowd; a box whose overlap is below the best so far
+ *              is skipped, so an overlap equal to the threshold matches and of two equal overlaps the later box wins;
+ *   dt_ignore  (num_det, num_area, num_thr) bytes: the matched box's ignore byte, or, unmatched, area < lo or area > hi.
+ * Overlaps stay in LDS while D * G <= FRCNN_COCO_LDS_IOUS and are read back from `ious` above that; the per-walk matched
+ * set is a register mask up to FRCNN_COCO_MASK_GT boxes and bytes in ws above that: pass max_gt_per_pair (the largest gt
+ * count of a pair) to both calls, ws_bytes() is 0 up to that count.  A pair with more boxes than max_gt_per_pair allowed
+ * for gets dt_match -2 and is not scored; a pair whose offsets leave no room in `ious` is not written at all.
+ * FRCNN_ERR_ARG: a negative count, num_thr or num_area below 1, a null required pointer.  num_pairs == 0 returns without
+ * a launch.  No allocation, no host synchronisation, one kernel launch. */
+#define FRCNN_COCO_PAIRS_PER_WG 4
+#define FRCNN_COCO_LDS_IOUS 1024
+#define FRCNN_COCO_MASK_GT 64
+size_t frcnn_coco_match_ws_bytes(int num_gt, int max_gt_per_pair, int num_area, int num_thr);
+int frcnn_coco_match(const double* det, const int* det_offsets, int num_det, const double* gt, const uint8_t* gt_crowd,
+                     const int* gt_offsets, int num_gt, const int64_t* iou_offsets, int64_t num_iou, int num_pairs,
+                     const double* iou_thrs, int num_thr, const double* area_rng, int num_area, int max_gt_per_pair,
+                     double* ious, int* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore, void* ws, size_t ws_bytes,
+                     void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training path (BASELINE config 4: FPN forward + backward of one train_step, lib/model/train_val.py:458)
  * ------------------------------------------------------------------------------------------- */
