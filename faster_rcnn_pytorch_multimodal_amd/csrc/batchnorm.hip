@@ -69,7 +69,7 @@ __device__ __forceinline__ void bn_bwd_final(double s, double q, int c, int C, c
 
 // part[g][c] = (sum_m a[m][c], sum_m b[m][c]) over the rows of group g, where
 //   forward : a = y,  b = y*y
-//   backward: a = g,  b = g * xhat     with g = relu ? (out > 0 ? dout : 0) : dout,  xhat = (y - mean) * invstd in fp64
+//   backward: a = g,  b = g * xhat     with g = relu ? (out <= 0 ? 0 : dout) : dout,  xhat = (y - mean) * invstd in fp64
 template <bool BWD>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ y, const float* __restrict__ dout,
                                                         const float* __restrict__ out, const float* __restrict__ mean,
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
       const size_t i = (size_t)m * C + c;
       if (BWD) {
         float g = dout[i];
-        if (relu && !(out[i] > 0.f)) g = 0.f;
+        if (relu && !frcnn::relu_open(out[i])) g = 0.f;
         // xhat in fp64 here: rounded to fp32 first, the sum would carry 2^-23 sum|g xhat|, and where d_gamma cancels
         // (|sum g xhat| << sum |g xhat|) that is many ulps of k = d_gamma / M in every element of dy
         const double xh = ((double)y[i] - (double)mu) * (double)is;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void bn_fwd_apply_kernel(const float* __restri
       for (int e = 0; e < 4; ++e) o[e] = o[e] + r[e];
     }
     if (relu)
-      for (int e = 0; e < 4; ++e) o[e] = o[e] > 0.f ? o[e] : 0.f;
+      for (int e = 0; e < 4; ++e) o[e] = frcnn::relu_f32(o[e]);
     reinterpret_cast<f32x4*>(out)[i] = o;
   }
 }
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     f32x4 g = reinterpret_cast<const f32x4*>(dout)[i];
     if (relu) {
       const f32x4 o = reinterpret_cast<const f32x4*>(out)[i];
-      for (int e = 0; e < 4; ++e) g[e] = o[e] > 0.f ? g[e] : 0.f;
+      for (int e = 0; e < 4; ++e) g[e] = frcnn::relu_open(o[e]) ? g[e] : 0.f;
     }
     if (dres) reinterpret_cast<f32x4*>(dres)[i] = g;
     const f32x4 v = reinterpret_cast<const f32x4*>(y)[i];

@@ -20,6 +20,15 @@ inline int check_launch(const char* what) {
 }
 
 __host__ __device__ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The activations of the feature path as torch evaluates them ("Non-finite values"): relu(NaN) is NaN, a NaN
+// compares false with the cap and stays, and the backward mask is x <= 0 ? 0 : g - it is OPEN where the activation is NaN.
+// fmaxf / fminf return the other operand for a NaN and would erase it; IEEE 754-2019 maximum / minimum propagate it, and gfx950
+// has them as one instruction (v_maximum3_f32 / v_minimum3_f32), where compare-and-select takes two (profiles/nonfinite.md).
+__device__ __forceinline__ float relu_f32(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ float cap_f32(float v, float cap) { return __builtin_elementwise_minimum(v, cap); }
+__device__ __forceinline__ bool relu_open(float y) { return !(y <= 0.f); }
+
 inline int next_pow2(int v) {
   int p = 1;
   while (p < v) p <<= 1;

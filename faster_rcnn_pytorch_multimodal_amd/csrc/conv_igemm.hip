@@ -124,8 +124,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
           for (int e = 0; e < 4; ++e) {
             float t = acc[i][j][4 * g + e] * sc[e] + sh[e];
             t += rv[g][e];
-            t = p.relu ? fmaxf(t, 0.f) : t;
-            if (p.mask) t = mv[g][e] > 0.f ? t * ms[e] : 0.f;
+            t = p.relu ? frcnn::relu_f32(t) : t;
+            if (p.mask) t = frcnn::relu_open(mv[g][e]) ? t * ms[e] : 0.f;
             v[e] = t;
           }
           *reinterpret_cast<f32x4*>(p.y + orow + n) = v;
@@ -139,8 +139,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
           if (slab) { slab[row + n] = acc[i][j][r]; continue; }
           float t = acc[i][j][r] * (p.scale ? p.scale[n] : 1.f) + (p.shift ? p.shift[n] : 0.f);
           if (p.res) t += p.res[orow + n];
-          t = p.relu ? fmaxf(t, 0.f) : t;
-          if (p.mask) t = p.mask[orow + n] > 0.f ? t * (p.mscale ? p.mscale[n] : 1.f) : 0.f;
+          t = p.relu ? frcnn::relu_f32(t) : t;
+          if (p.mask) t = frcnn::relu_open(p.mask[orow + n]) ? t * (p.mscale ? p.mscale[n] : 1.f) : 0.f;
           p.y[orow + n] = t;
         }
       }
@@ -209,8 +209,8 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvParams& p, f32x16 (&
         for (int e = 0; e < 4; ++e) {
           float t = v[it][e] * sc[e] + sh[e];
           t += rv[it][e];
-          t = p.relu ? fmaxf(t, 0.f) : t;
-          if (p.mask) t = mv[it][e] > 0.f ? t * ms[e] : 0.f;
+          t = p.relu ? frcnn::relu_f32(t) : t;
+          if (p.mask) t = frcnn::relu_open(mv[it][e]) ? t * ms[e] : 0.f;
           o[e] = t;
         }
         *reinterpret_cast<f32x4*>(p.y + at[it]) = o;
@@ -1216,8 +1216,8 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue(const float* __restr
     const int n = (int)(o % K);
     v = v * (scale ? scale[n] : 1.f) + (shift ? shift[n] : 0.f);
     if (res) v += res[o];
-    if (relu) v = fmaxf(v, 0.f);
-    if (mask) v = mask[o] > 0.f ? v * (mscale ? mscale[n] : 1.f) : 0.f;
+    if (relu) v = frcnn::relu_f32(v);
+    if (mask) v = frcnn::relu_open(mask[o]) ? v * (mscale ? mscale[n] : 1.f) : 0.f;
     y[o] = v;
   }
 }

@@ -227,14 +227,14 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
       f32x4 v = o[a][b] * sc + sh;
       if (relu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        for (int e = 0; e < 4; ++e) v[e] = frcnn::relu_f32(v[e]);
       }
       const size_t at = ((size_t)(n * H + ho) * W + wo) * K4 + k4;
       if (mask) {
         const f32x4 mv = reinterpret_cast<const f32x4*>(mask)[at];
         const f32x4 ms = mscale ? reinterpret_cast<const f32x4*>(mscale)[k4] : f32x4{1.f, 1.f, 1.f, 1.f};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = mv[e] > 0.f ? v[e] * ms[e] : 0.f;
+        for (int e = 0; e < 4; ++e) v[e] = frcnn::relu_open(mv[e]) ? v[e] * ms[e] : 0.f;
       }
       reinterpret_cast<f32x4*>(y)[at] = v;
     }

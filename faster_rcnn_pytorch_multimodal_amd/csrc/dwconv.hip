@@ -22,10 +22,10 @@ constexpr int kMaxBlocks = 256;      // one workgroup per CU: a lane has 3 * (kS
 
 __device__ __forceinline__ f32x4 splat(float v) { return f32x4{v, v, v, v}; }
 __device__ __forceinline__ f32x4 vmin(f32x4 a, float cap) {
-  return f32x4{fminf(a[0], cap), fminf(a[1], cap), fminf(a[2], cap), fminf(a[3], cap)};
+  return f32x4{frcnn::cap_f32(a[0], cap), frcnn::cap_f32(a[1], cap), frcnn::cap_f32(a[2], cap), frcnn::cap_f32(a[3], cap)};
 }
 __device__ __forceinline__ f32x4 vmax0(f32x4 a) {
-  return f32x4{fmaxf(a[0], 0.f), fmaxf(a[1], 0.f), fmaxf(a[2], 0.f), fmaxf(a[3], 0.f)};
+  return f32x4{frcnn::relu_f32(a[0]), frcnn::relu_f32(a[1]), frcnn::relu_f32(a[2]), frcnn::relu_f32(a[3])};
 }
 
 // lanes: number of working threads, a multiple of C4 (so c4 = thread % C4 is fixed for the launch); items = N * OH * strips.
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void clamp_max_kernel(float* __restrict__
     *p = vmin(*p, cap);
   }
   const size_t i = vecs * 4 + tid;      // count % 4 trailing elements
-  if (i < count) x[i] = fminf(x[i], cap);
+  if (i < count) x[i] = frcnn::cap_f32(x[i], cap);
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -2,7 +2,7 @@
 // streaming kernels MobileNet-v1 needs under loss.backward() (lib/nets/mobilenet_v1.py:117-123, lib/model/train_val.py:458).
 // NHWC, fp32.
 //
-// Both depthwise gradients read the MASKED upstream gradient dz = dy * scale * m, m = [relu off or y > 0] * [y < out_cap]
+// Both depthwise gradients read the MASKED upstream gradient dz = dy * scale * m, m = [relu off or not y <= 0] * [not y >= out_cap]
 // (hardtanh's backward: zero at both closed ends), computed from dy and the forward's stored output y as they are loaded and
 // never stored.  As in the forward, one lane owns ONE float4 of channels for the whole launch and keeps the taps and the
 // folded scale in registers, a work item is a strip of FRCNN_DWCONV_STRIP pixels along W, every load is clamped into bounds
@@ -32,10 +32,10 @@ static_assert(kFinalLanes * kFinalLanes == kThreads, "final sum: one workgroup i
 
 __device__ __forceinline__ f32x4 splat(float v) { return f32x4{v, v, v, v}; }
 __device__ __forceinline__ f32x4 vmin(f32x4 a, float cap) {
-  return f32x4{fminf(a[0], cap), fminf(a[1], cap), fminf(a[2], cap), fminf(a[3], cap)};
+  return f32x4{frcnn::cap_f32(a[0], cap), frcnn::cap_f32(a[1], cap), frcnn::cap_f32(a[2], cap), frcnn::cap_f32(a[3], cap)};
 }
 __device__ __forceinline__ float mask1(float g, float y, float cap, int relu) {
-  return ((!relu || y > 0.f) && y < cap) ? g : 0.f;
+  return ((relu && y <= 0.f) || y >= cap) ? 0.f : g;   // hardtanh_backward: open for a NaN y
 }
 // dz of one float4: g = dy * scale already; y is read only when MASK
 template <bool MASK>

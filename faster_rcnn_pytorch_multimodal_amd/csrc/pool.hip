@@ -6,11 +6,20 @@
 
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// torch's update rule (val > max || isnan(val)), pairwise: a NaN on either side wins
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ f32x4 nan_max4(f32x4 a, f32x4 b) {
+  f32x4 m;
+  m[0] = nan_max(a[0], b[0]); m[1] = nan_max(a[1], b[1]); m[2] = nan_max(a[2], b[2]); m[3] = nan_max(a[3], b[3]);
+  return m;
+}
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // MaxPool 3x3 / stride 2 / pad 1, NHWC (lib/nets/resnet.py:156).  One thread = 4 channels of one
 // output pixel; consecutive threads walk the channel dimension -> 16-byte coalesced accesses.
+// max is torch's: a NaN in a window makes that output NaN (it beats +inf).
 // ------------------------------------------------------------------------------------------------
 namespace {
 __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc(const float* __restrict__ x, float* __restrict__ y, int N,
@@ -33,7 +42,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc(const float* __restrict
         const int wi = wo * 2 - 1 + dx;
         if ((unsigned)wi >= (unsigned)W) continue;
         const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((size_t)n * H + hi) * W + wi) * C4 * 4 + c4 * 4);
-        m[0] = fmaxf(m[0], v[0]); m[1] = fmaxf(m[1], v[1]); m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
+        m = nan_max4(m, v);
       }
     }
     *reinterpret_cast<f32x4*>(y + i * 4) = m;
@@ -63,7 +72,8 @@ extern "C" int frcnn_maxpool3x3s2_fwd(const float* x, float* y, int n, int h, in
 
 // Backward of the 3x3/2 max-pool (autograd of nn.MaxPool2d in the trainable stem, cfg.RESNET.FIXED_BLOCKS == -1):
 // gather form, deterministic.  An input pixel lies in at most 2 x 2 windows; it receives dy of a window when it is that
-// window's FIRST maximum in row-major scan order (the index torch's forward stores).
+// window's winner in torch's row-major scan (the index its forward stores): an element takes over when val > max ||
+// isnan(val) - the FIRST of equal maxima, and the LAST NaN of a window that holds one.
 namespace {
 __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_nhwc(const float* __restrict__ x, const float* __restrict__ dy,
                                                             float* __restrict__ dx, int N, int H, int W, int C4, int Ho,
@@ -80,7 +90,8 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_nhwc(const float* __rest
     f32x4 g = {0.f, 0.f, 0.f, 0.f};
     for (int ho = max(0, (h - 1 + 1) / 2); ho <= min(Ho - 1, (h + 1) / 2); ++ho)
       for (int wo = max(0, (w - 1 + 1) / 2); wo <= min(Wo - 1, (w + 1) / 2); ++wo) {
-        // is (h, w) the first maximum of window (ho, wo)?  earlier = strictly before in row-major order
+        // is (h, w) the winner of window (ho, wo)?  earlier = strictly before in row-major order.  A finite pixel loses to
+        // any NaN (both comparisons are false); a NaN pixel loses only to a later NaN.
         bool first[4] = {true, true, true, true};
         for (int dyy = 0; dyy < 3; ++dyy) {
           const int hi = ho * 2 - 1 + dyy;
@@ -90,7 +101,8 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_nhwc(const float* __rest
             if ((unsigned)wi >= (unsigned)W || (hi == h && wi == w)) continue;
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((size_t)n * H + hi) * W + wi) * C4 * 4 + c4 * 4);
             const bool earlier = hi < h || (hi == h && wi < w);
-            for (int e = 0; e < 4; ++e) first[e] = first[e] && (earlier ? v[e] < me[e] : v[e] <= me[e]);
+            for (int e = 0; e < 4; ++e)
+              first[e] = first[e] && (me[e] != me[e] ? (earlier || v[e] == v[e]) : (earlier ? v[e] < me[e] : v[e] <= me[e]));
           }
         }
         const f32x4 d = *reinterpret_cast<const f32x4*>(dy + ((((size_t)n * Ho + ho) * Wo + wo) * C4 + c4) * 4);
@@ -124,14 +136,6 @@ extern "C" int frcnn_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx
 namespace {
 constexpr int kPool2Threads = 256;
 constexpr int kPool2MaxBlocks = FRCNN_MAXPOOL2X2_MAX_LANES / kPool2Threads;   // 8 workgroups per CU
-
-// torch's update rule (val > max || isnan(val)), pairwise: a NaN on either side wins
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ f32x4 nan_max4(f32x4 a, f32x4 b) {
-  f32x4 m;
-  m[0] = nan_max(a[0], b[0]); m[1] = nan_max(a[1], b[1]); m[2] = nan_max(a[2], b[2]); m[3] = nan_max(a[3], b[3]);
-  return m;
-}
 
 __global__ __launch_bounds__(kPool2Threads) void maxpool2x2s2_nhwc(const f32x4* __restrict__ x, f32x4* __restrict__ y, int H,
                                                                    int W, int C4, int Ho, int Wo, unsigned long long total) {
@@ -174,7 +178,7 @@ extern "C" int frcnn_maxpool2x2s2_fwd(const float* x, float* y, int n, int h, in
 // load - every element of dx is written by the launch, no memset.  The winner is torch's: scan (0,0), (0,1), (1,0), (1,1),
 // an element takes over when val > max || isnan(val) - the first of equal values, the last NaN, (0,0) of four -inf.
 // relu_mask: x is the ReLU output of the convolution in front of the pool and dx the gradient of its pre-activation - the
-// winner receives dy only if x[winner] > 0 (act_bwd_kernel's v > 0.f ? g : 0.f), so no act_bwd pass over dx follows.
+// winner receives dy unless x[winner] <= 0 (act_bwd_kernel's rule: open for a NaN), so no act_bwd pass over dx follows.
 // No atomics, no LDS, deterministic; the same bounded grid and 64-bit grid-stride loop as the forward.
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(kPool2Threads) void maxpool2x2s2_bwd_nhwc(const f32
       if (v01[e] > m || v01[e] != v01[e]) { m = v01[e]; win = 1; }
       if (v10[e] > m || v10[e] != v10[e]) { m = v10[e]; win = 2; }
       if (v11[e] > m || v11[e] != v11[e]) { m = v11[e]; win = 3; }
-      const float ge = relu_mask ? (m > 0.f ? g[e] : 0.f) : g[e];
+      const float ge = relu_mask ? (frcnn::relu_open(m) ? g[e] : 0.f) : g[e];
       d00[e] = win == 0 ? ge : 0.f;
       d01[e] = win == 1 ? ge : 0.f;
       d10[e] = win == 2 ? ge : 0.f;

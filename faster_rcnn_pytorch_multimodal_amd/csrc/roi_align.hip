@@ -33,7 +33,7 @@ struct RoiEpilogue {
       const float4 b = reinterpret_cast<const float4*>(shift)[c4];
       v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
     }
-    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (relu) { v.x = frcnn::relu_f32(v.x); v.y = frcnn::relu_f32(v.y); v.z = frcnn::relu_f32(v.z); v.w = frcnn::relu_f32(v.w); }
     return v;
   }
 };
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256) void roi_align_fwd_planned(const float* __rest
   auto finish = [&](float4 v) {
     if (EPI) {
       v.x = v.x * esc.x + esh.x; v.y = v.y * esc.y + esh.y; v.z = v.z * esc.z + esh.z; v.w = v.w * esc.w + esh.w;
-      if (epi.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (epi.relu) { v.x = frcnn::relu_f32(v.x); v.y = frcnn::relu_f32(v.y); v.z = frcnn::relu_f32(v.z); v.w = frcnn::relu_f32(v.w); }
     }
     return v;
   };

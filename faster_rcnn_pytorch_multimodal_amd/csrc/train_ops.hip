@@ -14,7 +14,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------
-// y = act(conv*scale + shift + res)  ->  dz = relu ? (y > 0 ? dy : 0) : dy ; d_res = dz ; d_conv = dz*scale
+// y = act(conv*scale + shift + res)  ->  dz = relu ? (y <= 0 ? 0 : dy) : dy ; d_res = dz ; d_conv = dz*scale
 // (autograd of F.relu / eval-mode batch_norm / the residual add in lib/nets/resnet.py:98-127).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
     f32x4 g = reinterpret_cast<const f32x4*>(dy)[i];
     if (relu) {
       const f32x4 v = reinterpret_cast<const f32x4*>(y)[i];
-      for (int e = 0; e < 4; ++e) g[e] = v[e] > 0.f ? g[e] : 0.f;
+      for (int e = 0; e < 4; ++e) g[e] = relu_open(v[e]) ? g[e] : 0.f;
     }
     if (d_res) reinterpret_cast<f32x4*>(d_res)[i] = g;
     if (scale) {

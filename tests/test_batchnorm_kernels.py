@@ -487,6 +487,8 @@ def test_columns_are_independent(hip, poison):
     for name in OUTPUTS:
         assert _bits_equal(clean[name][..., others], dirty[name][..., others]), name
     assert not bool(torch.isfinite(dirty["mean"][j]))
+    # and the poisoned channel shows it behind the ReLU: its statistics are non-finite, so every row of it is (torch gives NaN)
+    assert not bool(torch.isfinite(dirty["out"][:, j]).any())
 
 
 @pytest.mark.gpu

@@ -21,8 +21,10 @@ Which case reaches which regime (case ids as pytest prints them):
                                    44x50-45x53 with N = 1000 (1000 x 45 x 53 and 1000 x 44 x 50 items > 8192 * 256: second trip, both ways)
   upsample, output < input         rejected by both entry points: the FPN's top-down path only enlarges (nets/fpn.py)
   maxpool maps                     1x1 1x9 9x1 2x2 7x8; fwd 1x726x726x64 (363 x 363 x 16 items > 8192 * 256); bwd 1x1450x1450x4
-  maxpool inputs                   randn, neg (all negative: a zero pad would win), inf (-inf, whole windows of it)
-  maxpool backward                 ties (integers in -3..3) against autograd; conservation sum(dx) == sum(dy) per channel
+  maxpool inputs                   randn, neg (all negative: a zero pad would win), inf (-inf, whole windows of it), nan (windows with
+                                   none, one and several NaN, one in the padding-adjacent corner), nan+inf (+inf beside them: NaN wins)
+  maxpool backward                 ties (integers in -3..3) against autograd; conservation sum(dx) == sum(dy) per channel;
+                                   nan: a window that holds a NaN hands its dy to its last NaN, as autograd does
   pad_channels                     1-4, 3-4, 3-8, 4-4 (a copy, through the C ABI), big (525000 x 4 > 8192 * 256)
   prep_image scales                1.0 (bit-exact (px - mean) / std), 0.5 on 37 x 53 (18.5 -> 18, 26.5 -> 26: half-even), 0.3, 1.3, 2.0, 3.7
   prep_image images                1x1, 1x40, 40x1 (where the output is not empty), 37x53, 1100x1000 at 1.0 (> 4096 * 256 pixels)
@@ -375,7 +377,8 @@ def test_upsample_rejects_an_output_smaller_than_the_input(hip, shape):
 # 3. maxpool3x3s2_fwd / _bwd, pad_channels
 # ================================================================================================
 POOL_MAPS = [(1, 1), (1, 9), (9, 1), (2, 2), (7, 8)]
-POOL_KINDS = ["randn", "neg", "inf"]
+POOL_KINDS = ["randn", "neg", "inf", "nan", "nan+inf"]
+POOL_BWD_KINDS = ["ties", "nan"]
 POOL_FWD_BIG = (1, 726, 726, 64)
 POOL_BWD_BIG = (1, 1450, 1450, 4)
 
@@ -387,11 +390,19 @@ def _pool_input(shape, kind, g):
     elif kind == "inf":
         x[torch.rand(shape, generator=g) < 0.4] = float("-inf")
         x[:, : (shape[1] + 1) // 2, : (shape[2] + 1) // 2] = float("-inf")       # whole windows of -inf as well
+    elif kind in ("nan", "nan+inf"):
+        # a quarter of the pixels NaN: windows with none, one and several of them (the 1x1 map: its only pixel, channel 0);
+        # "nan+inf": +inf next to them, which a NaN must beat
+        if kind == "nan+inf":
+            x[torch.rand(shape, generator=g) < 0.3] = float("inf")
+        x[torch.rand(shape, generator=g) < 0.25] = float("nan")
+        x[0, 0, 0, 0] = float("nan")                           # the corner next to the padding
     return x
 
 
 def pool_fwd32(x):
-    """maxpool3x3s2_nhwc: running fmaxf from -inf over the window positions that lie inside the map."""
+    """maxpool3x3s2_nhwc: torch's running update (v > m || isnan(v)) from -inf over the window positions that lie inside the
+    map - a NaN takes over and is never replaced by a number."""
     n, h, w, c = x.shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     xp = np.full((n, 2 * ho + 1, 2 * wo + 1, c), -np.inf, f32)
@@ -399,19 +410,22 @@ def pool_fwd32(x):
     m = np.full((n, ho, wo, c), -np.inf, f32)
     for dy in range(3):
         for dx in range(3):
-            m = np.maximum(m, xp[:, dy:dy + 2 * ho:2, dx:dx + 2 * wo:2])
+            v = xp[:, dy:dy + 2 * ho:2, dx:dx + 2 * wo:2]
+            m = np.where((v > m) | np.isnan(v), v, m)
     return m
 
 
 def pool_bwd32(x, dy):
-    """maxpool3x3s2_bwd_nhwc: each window hands its dy to its first maximum in row-major order; a pixel adds the windows it
-    wins in (ho, wo) order."""
+    """maxpool3x3s2_bwd_nhwc: each window hands its dy to its winner in torch's row-major scan - the first maximum, or the LAST
+    NaN of a window that holds one; a pixel adds the windows it wins in (ho, wo) order."""
     n, h, w, c = x.shape
     ho, wo = dy.shape[1], dy.shape[2]
     xp = np.full((n, 2 * ho + 1, 2 * wo + 1, c), -np.inf, f32)
     xp[:, 1:h + 1, 1:w + 1] = x
     win = np.stack([xp[:, a:a + 2 * ho:2, b:b + 2 * wo:2] for a in range(3) for b in range(3)], -1)      # (n, ho, wo, c, 9)
-    first = win.argmax(-1)                                     # numpy returns the first maximum
+    nan = np.isnan(win)
+    first = np.where(nan, -np.inf, win).argmax(-1)             # numpy returns the first maximum
+    first = np.where(nan.any(-1), 8 - nan[..., ::-1].argmax(-1), first)      # the last NaN
     hi = 2 * np.arange(ho)[None, :, None, None] - 1 + first // 3
     wi = 2 * np.arange(wo)[None, None, :, None] - 1 + first % 3
     dx = np.zeros((n, h, w, c), f32)
@@ -432,9 +446,13 @@ def pool_fwd_case(shape, kind):
 
 
 @functools.lru_cache(maxsize=None)
-def pool_bwd_case(shape):
+def pool_bwd_case(shape, kind="ties"):
     g = torch.Generator().manual_seed(500 + sum(shape))
     x = torch.randint(-3, 4, shape, generator=g).float()       # many ties inside every window
+    if kind == "nan":                                          # windows with none, one and several NaN; +inf that must lose to them
+        x[torch.rand(shape, generator=g) < 0.15] = float("inf")
+        x[torch.rand(shape, generator=g) < 0.25] = float("nan")
+        x[0, 0, 0, 0] = float("nan")
     xr = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
     y = F.max_pool2d(xr, 3, 2, 1)
     dy = torch.randn(y.shape, generator=g)
@@ -463,11 +481,27 @@ def test_cpu_restatement_maxpool_fwd(case):
         assert float(ref.max()) < 0
     if kind == "inf":
         assert bool(torch.isinf(ref).any())
+    if kind in ("nan", "nan+inf"):                             # torch: a window that holds a NaN gives NaN, also next to +inf
+        xn = torch.where(torch.isnan(x), torch.ones_like(x), torch.zeros_like(x))
+        holds = F.max_pool2d(xn.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1) > 0
+        assert torch.equal(torch.isnan(ref), holds) and bool(holds.any())
+        assert h * w == 1 or not bool(holds.all())
 
 
 @pytest.mark.parametrize("hw", POOL_MAPS, ids=lambda m: "%dx%d" % m)
 def test_cpu_restatement_maxpool_bwd(hw):
-    inp, ref, bars = pool_bwd_case((2, hw[0], hw[1], 8))
+    _cpu_restatement_maxpool_bwd(hw, "ties")
+
+
+@pytest.mark.parametrize("hw", POOL_MAPS, ids=lambda m: "%dx%d" % m)
+def test_cpu_restatement_maxpool_bwd_nan(hw):
+    _cpu_restatement_maxpool_bwd(hw, "nan")
+
+
+def _cpu_restatement_maxpool_bwd(hw, kind):
+    inp, ref, bars = pool_bwd_case((2, hw[0], hw[1], 8), kind)
+    if kind == "nan":                                          # torch hands a window's dy to a NaN of it: finite gradients on NaN pixels
+        assert bool((ref[torch.isnan(inp["x"])] != 0).any()) and bool(torch.isfinite(ref).all())
     dx = pool_bwd32(_np(inp["x"]), _np(inp["dy"]))
     _assert_close("maxpool_bwd", "%dx%d" % hw, "dx", dx, ref, bars["dx"], "cpu", HEADROOM)
     _assert_close("maxpool_bwd", "%dx%d" % hw, "conservation", dx.astype(np.float64).sum((0, 1, 2)),
@@ -488,7 +522,17 @@ def test_maxpool_fwd_edges(hip, case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(2, h, w, 8) for h, w in POOL_MAPS] + [POOL_BWD_BIG], ids=lambda s: "%dx%dx%dx%d" % s)
 def test_maxpool_bwd_edges(hip, shape):
-    inp, ref, bars = pool_bwd_case(shape)
+    _maxpool_bwd_edges(shape, "ties")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", POOL_MAPS, ids=lambda m: "%dx%d" % m)
+def test_maxpool_bwd_routes_a_window_to_its_nan(hip, hw):
+    _maxpool_bwd_edges((2, hw[0], hw[1], 8), "nan")
+
+
+def _maxpool_bwd_edges(shape, kind):
+    inp, ref, bars = pool_bwd_case(shape, kind)
     if shape == POOL_BWD_BIG:
         assert inp["x"].numel() // 4 > GRID_CAP
     dx = _ops().maxpool3x3s2_bwd(inp["x"].to(DEV), inp["dy"].to(DEV))
@@ -504,7 +548,7 @@ def test_maxpool_bwd_edges(hip, shape):
     holds = torch.zeros(x.shape, dtype=torch.bool)
     for r_ in rows:
         for c_ in cols:
-            holds |= x == y[:, r_][:, :, c_]
+            holds |= (x == y[:, r_][:, :, c_]) | (torch.isnan(x) & torch.isnan(y[:, r_][:, :, c_]))
     touched = dx.cpu() != 0
     assert bool(touched.any()) and bool(holds[touched].all())
 
