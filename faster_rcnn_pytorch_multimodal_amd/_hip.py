@@ -193,6 +193,12 @@ PROTOTYPES = {
     "frcnn_filter_per_class": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int,
                                        c_int, _P, _P, _P, _P, c_size_t, _P]),
     "frcnn_sgd_update": (c_int, [_P, _P, c_int64, _P, _P, c_int, _P, c_int64, c_float, c_float, c_int, _P]),
+    "frcnn_canvas_from_image_blob": (c_int, [_P, c_int, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int), _P, _P]),
+    "frcnn_canvas_from_bev_blob_ws_bytes": (c_size_t, []),
+    "frcnn_canvas_from_bev_blob": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "frcnn_draw_plan": (c_int, [_P, _P] + [c_int] * 8 + [_P, _P] + [c_int] * 3 + [_P, c_int, _P]),
+    "frcnn_draw_scatter": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
+    "frcnn_draw_compose": (c_int, [_P, c_int, _P, _P, c_int, c_int, _P]),
 }
 
 

@@ -48,6 +48,7 @@ SOURCES = {
     "coco_match.hip": ["-ffp-contract=off"],
     "optim.hip": ["-ffp-contract=off"],
     "nms_rotated.hip": ["-ffp-contract=off"],
+    "draw.hip": ["-ffp-contract=off"],
 }
 COMMON_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

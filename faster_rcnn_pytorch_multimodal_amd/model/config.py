@@ -83,6 +83,7 @@ def _defaults():
                   CONV_SPLIT_BF16=True,    # not in the reference: TEST-mode convolutions the library's rule selects (frcnn_conv2d_split_bf16_wanted: the large layer4 / projection GEMMs) run as fp32-accurate split-bf16 GEMMs - each operand as three bf16 planes, six products per k-group (nets/hip_modules.conv_forward, profiles/conv_split_bf16.md).  CONV_BF16 takes precedence; training ignores it
                   FRAMES_IN_FLIGHT=4,      # test_net: frames in flight, one HIP stream each
                   GRAPH_MAX_SHAPES=4,      # distinct frame problems held as graphs (least recently used one is dropped)
+                  DRAW_LIDAR_BOXES=True,   # not in the reference (its footprint calls are commented out at waymo_lidb.py:282,302), LiDAR only: test_net(draw_det=True) draws the ground-truth and detection footprints on the BEV map; False gives the reference's literal picture, the map alone
                   GRAPH_AUTOTUNE=True)     # time the convolution plans of a new frame shape during its warm-up frames
     c.RESNET = dict(MAX_POOL=False, FIXED_BLOCKS=1)
     # lib/model/config.py:295-308 (nets/mobilenet_v1.py)
@@ -90,6 +91,7 @@ def _defaults():
     c.PIXEL_MEANS = np.array([[[96.866, 98.76, 93.85]]])
     c.PIXEL_STDDEVS = np.array([[[1, 1, 1]]])
     c.PIXEL_ARRANGE = [0, 1, 2]
+    c.PIXEL_ARRANGE_BGR = [2, 1, 0]        # config.py:344: blob channel order -> picture channel order (model/draw.py)
     c.GRAD_MAX_CLIP = 20
     c.RNG_SEED = 3
     c.POOLING_MODE = 'align'               # config.py:364

@@ -64,6 +64,20 @@ class ReferenceDb:
     def evaluate_detections(self, all_boxes, out_dir, mode):
         return self.inner.evaluate_detections(all_boxes, out_dir, mode)
 
+    def file_at(self, i, mode):
+        return self.inner.path_at(i, mode)
+
+    def gt_at(self, i, mode):
+        """lib/model/test.py:233: the roidb entry of frame i's file ({'boxes', 'gt_classes', ...}) or None.  The reference
+        looks in the validation roidb whatever the mode."""
+        if not hasattr(self.inner, 'find_gt_for_frame'):
+            return None
+        return self.inner.find_gt_for_frame(self.inner.path_at(i, mode), 'val')
+
+    @property
+    def _uncertainty_sort_type(self):
+        return getattr(self.inner, '_uncertainty_sort_type', None)
+
     @staticmethod
     def wraps(db):
         return not hasattr(db, 'blobs_at') and (hasattr(db, '_val_index') or hasattr(db, '_test_index'))
@@ -155,7 +169,13 @@ def test_net(net, db, out_dir, max_dets=100, thresh=0.1, mode='test', draw_det=F
     ``db``: either an object with the reference's dataset protocol (``_val_index`` / ``_test_index``, ``path_at``,
     ``num_classes``, ``name``, ``evaluate_detections``; wrapped in ``ReferenceDb``, frames loaded by ``_get_blobs``), or a
     frame source with ``num_classes``, ``num_frames(mode)``, ``blobs_at(i, mode)`` -> {'data': (1,H,W,C) blob or None,
-    'info': 7-vector}, optional ``name_at(i, mode)``, optional ``evaluate_detections(all_boxes, out_dir, mode)``.
+    'info': 7-vector}, optional ``name_at(i, mode)``, optional ``evaluate_detections(all_boxes, out_dir, mode)``, optional
+    ``gt_at(i, mode)`` -> {'boxes', 'gt_classes'} or None and ``_uncertainty_sort_type`` (both read by ``draw_det`` only).
+    ``draw_det``: every frame is also rendered on the device, on its lane's stream behind its record (``model/draw.py``:
+    canvas from the blob, the stored rows - after the ``max_dets`` cut, the reference draws before it - and the ground
+    truth as outlines in the reference's painter's order), copied out through a bounded ring and written by encoder threads as
+    ``<get_output_dir(db, 'test')>/test_drawn/{img-,iter_0_}<frame>.png`` by the rank that ran the frame; the folder is
+    emptied first (lib/model/test.py:176,231-242).  False: nothing is allocated or launched and no folder is made.
     ``out_dir`` None / '' -> ``get_output_dir(db, mode='test')`` like the reference (:166), which ignores the argument.  Per frame everything stays on the device up to the
     per-class, max_dets-limited record (``detect_frame_device``); records are collated in blocks of
     ``collate.EVAL_GATHER_EVERY`` frames (one all-gather over the ranks + one device-to-host copy per block, on a stream of
@@ -169,8 +189,6 @@ def test_net(net, db, out_dir, max_dets=100, thresh=0.1, mode='test', draw_det=F
     import torch.distributed as dist
     from ..datasets import voc_eval
     from . import collate
-    if draw_det:
-        raise NotImplementedError("drawing is dataset tooling, outside the accelerated path")
     np.random.seed(cfg.RNG_SEED)
     if ReferenceDb.wraps(db):
         db = ReferenceDb(db)
@@ -215,6 +233,16 @@ def test_net(net, db, out_dir, max_dets=100, thresh=0.1, mode='test', draw_det=F
     if rank == 0:
         os.makedirs(out_dir, exist_ok=True)
         writers = {j: open(os.path.join(out_dir, 'det_%s_cls%d.txt' % (mode, j)), 'wt') for j in range(1, k)}
+    canvases = None
+    if draw_det:
+        from . import draw
+        if rank == 0:
+            draw.reset_draw_folder(db, 'test')
+        if distributed:
+            dist.barrier()
+        os.makedirs(draw.draw_folder(db, 'test'), exist_ok=True)      # ranks on another node have a folder of their own
+        canvases = draw.CanvasRing(draw.draw_folder(db, 'test'), lanes, dev, lidar)
+        sort_key = getattr(db, '_uncertainty_sort_type', None)
 
     def queue_chunk(c0, n, ring):
         for s in range(c0, c0 + n):
@@ -232,6 +260,12 @@ def test_net(net, db, out_dir, max_dets=100, thresh=0.1, mode='test', draw_det=F
                     else:
                         dets, counts = detect_frame_device(net, blobs['data'], blobs['info'], thresh, max_dets, max_out)
                     collate.pack_record(dets, counts, slot)
+                    if canvases is not None:
+                        i = mine[s]
+                        gt = db.gt_at(i, mode) if hasattr(db, 'gt_at') else None
+                        name = (db.file_at(i, mode) if hasattr(db, 'file_at') else
+                                db.name_at(i, mode) if hasattr(db, 'name_at') else '%06d' % i)
+                        canvases.render(s % lanes, blobs['data'], blobs['info'], dets, counts, gt, sort_key, name)
                 else:
                     slot.zero_()          # a frame without data (the reference skips it, :198-203) or a padding step
                 ring.commit(s - c0)
@@ -265,19 +299,26 @@ def test_net(net, db, out_dir, max_dets=100, thresh=0.1, mode='test', draw_det=F
     rings = [collate.RecordRing(numel, min(chunk, max(steps, 1)), every=collate.EVAL_GATHER_EVERY, device=dev,
                                 distributed=distributed, gather_device=gather_dev) for _ in range(2 if steps > chunk else 1)]
     prev = None
-    for ci, c0 in enumerate(range(0, steps, chunk)):
-        n = min(chunk, steps - c0)
-        ring = rings[ci % len(rings)]
-        queue_chunk(c0, n, ring)
+    try:
+        for ci, c0 in enumerate(range(0, steps, chunk)):
+            n = min(chunk, steps - c0)
+            ring = rings[ci % len(rings)]
+            queue_chunk(c0, n, ring)
+            if prev is not None:
+                collect_chunk(*prev)
+            prev = (c0, n, ring)
         if prev is not None:
             collect_chunk(*prev)
-        prev = (c0, n, ring)
-    if prev is not None:
-        collect_chunk(*prev)
-    if pool is not None:
-        cur = torch.cuda.current_stream(dev)
-        for st in pool.streams:
-            cur.wait_stream(st)
+        if pool is not None:
+            cur = torch.cuda.current_stream(dev)
+            for st in pool.streams:
+                cur.wait_stream(st)
+        if canvases is not None:
+            canvases.close()              # every picture is on disk when the loop's time is taken
+    except BaseException:
+        if canvases is not None:
+            canvases.close(abort=True)    # the loop's error is the one to report; leave no encoder thread behind
+        raise
     if timers is not None:
         timers['loop_s'] = time.perf_counter() - t_loop
         timers['frames'] = len(mine)

@@ -2296,3 +2296,132 @@ def sgd_update(grad_flat, momentum_flat, segments_host, segments_dev, chunks_dev
                                     _ptr(segments_dev) if num else None, segments_host.ctypes.data if num else None, num,
                                     _ptr(chunks_dev) if chunks_dev.numel() else None, int(chunks_dev.shape[0]),
                                     float(momentum), float(clip), int(bool(zero_grads)), _stream()), "frcnn_sgd_update")
+
+
+# frcnn_draw_*: the draw list's row layout and kinds, the two BEV colourings (include/frcnn_hip.h FRCNN_DRAW_*)
+DRAW_ROW_INTS = 12
+DRAW_SKIP, DRAW_RECT, DRAW_FOOTPRINT = 0, 1, 2
+DRAW_BEV_FORMS = {'waymo': 0, 'kitti': 1}
+DRAW_MAX_OUT = 4096
+
+
+def _draw_dev(who, t, name, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _hip.HipError("%s: %s must be a tensor on the MI355X (got %s); this package has no CPU path"
+                            % (who, name, getattr(t, "device", type(t))))
+    if t.dtype != dtype or not t.is_contiguous():
+        raise _hip.HipError("%s: %s must be contiguous %s (got %s)" % (who, name, dtype, t.dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise _hip.HipError("%s: %s has shape %s, expected %s" % (who, name, tuple(t.shape), tuple(shape)))
+    return t
+
+
+def _draw_out(who, out, name, dtype, shape, device):
+    if out is None:
+        return torch.empty(tuple(shape), dtype=dtype, device=device)
+    return _draw_dev(who, out, name, dtype, shape)
+
+
+def canvas_from_image_blob(blob, out=None):
+    """The image blob back to a picture (frcnn_canvas_from_image_blob; lib/datasets/waymo_imdb.py:200-204): ``blob``
+    (1, H, W, 3) fp32 -> (H, W, 3) uint8, ``blob * cfg.PIXEL_STDDEVS + cfg.PIXEL_MEANS`` in float64, channels in
+    ``cfg.PIXEL_ARRANGE_BGR`` order, truncated toward zero, saturated to [0, 255], NaN -> 0."""
+    from .model.config import cfg
+    who = "canvas_from_image_blob"
+    _dev_f32(blob, who + ": blob")
+    if blob.dim() != 4 or blob.shape[0] != 1 or blob.shape[3] != 3:
+        raise _hip.HipError("%s: blob must be (1, H, W, 3), got %s" % (who, tuple(blob.shape)))
+    h, w = int(blob.shape[1]), int(blob.shape[2])
+    out = _draw_out(who, out, "out", torch.uint8, (h, w, 3), blob.device)
+    stds = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(cfg.PIXEL_STDDEVS, np.float64).reshape(-1)])
+    means = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(cfg.PIXEL_MEANS, np.float64).reshape(-1)])
+    arrange = (ctypes.c_int * 3)(*[int(v) for v in cfg.PIXEL_ARRANGE_BGR])
+    _hip.check(_hip.load().frcnn_canvas_from_image_blob(_ptr(blob), h, w, stds, means, arrange, _ptr(out), _stream()),
+               "frcnn_canvas_from_image_blob")
+    return out
+
+
+def canvas_from_bev_blob(blob, form, num_slices=None, out=None, ws=None):
+    """The BEV voxel grid as a picture (frcnn_canvas_from_bev_blob): ``blob`` (1, Ny, Nx, C) fp32 -> (Ny, Nx, 3) uint8,
+    ``form`` 'waymo' (lib/datasets/waymo_lidb.py:240-261) or 'kitti' (kitti_lidb.py:289-297, also CADC's).  The blob is
+    only read.  ``num_slices`` defaults to cfg.LIDAR.NUM_SLICES."""
+    from .model.config import cfg
+    who = "canvas_from_bev_blob"
+    _dev_f32(blob, who + ": blob")
+    if blob.dim() != 4 or blob.shape[0] != 1:
+        raise _hip.HipError("%s: blob must be (1, Ny, Nx, C), got %s" % (who, tuple(blob.shape)))
+    if form not in DRAW_BEV_FORMS:
+        raise _hip.HipError("%s: form %r, one of %s" % (who, form, sorted(DRAW_BEV_FORMS)))
+    ny, nx, c = (int(v) for v in blob.shape[1:])
+    slices = int(cfg.LIDAR.NUM_SLICES if num_slices is None else num_slices)
+    out = _draw_out(who, out, "out", torch.uint8, (ny, nx, 3), blob.device)
+    lib = _hip.load()
+    ws_bytes = lib.frcnn_canvas_from_bev_blob_ws_bytes()
+    ws = _given_workspace(who, ws, ws_bytes, blob.device)
+    _hip.check(lib.frcnn_canvas_from_bev_blob(_ptr(blob), ny, nx, c, slices, DRAW_BEV_FORMS[form], _ptr(out), _ptr(ws),
+                                              ws.numel() * ws.element_size(), _stream()), "frcnn_canvas_from_bev_blob")
+    return out
+
+
+def canvas_bev_workspace(device):
+    """A workspace for ``canvas_from_bev_blob`` (the per-workgroup extrema and the three factors)."""
+    return torch.empty(int(_hip.load().frcnn_canvas_from_bev_blob_ws_bytes()), dtype=torch.uint8, device=device)
+
+
+def draw_plan_capacity(num_classes, max_out, num_gt):
+    return (int(num_classes) - 1) * int(max_out) + int(num_gt)
+
+
+def draw_plan(dets, counts, canvas_hw, lidar, key=None, limiter0=15, limiter_resets=None, gt=None, gt_labels=None,
+              rows=None):
+    """A frame's device record -> its draw list in painter's order (frcnn_draw_plan; include/frcnn_hip.h has the rules).
+    ``dets`` (K, max_out, E) fp32 and ``counts`` (K,) int32 as ``detect_frame_device`` returns them; ``key``: None or
+    ``(first column, column count)`` of the uncertainty that orders a class's detections; ``gt`` (G, 4 or 7) fp32 and
+    ``gt_labels`` (G,) int32 device tensors or None; ``limiter_resets`` defaults to the reference's rule for the frame
+    kind (image: resets, LiDAR: carries).  Returns int32 (capacity, DRAW_ROW_INTS), capacity = (K-1) * max_out + G."""
+    who = "draw_plan"
+    _dev_f32(dets, who + ": dets")
+    if dets.dim() != 3:
+        raise _hip.HipError("%s: dets must be (K, max_out, E), got %s" % (who, tuple(dets.shape)))
+    k, max_out, elem = (int(v) for v in dets.shape)
+    _draw_dev(who, counts, "counts", torch.int32, (k,))
+    num_gt = 0
+    if gt is not None and gt.numel():
+        _draw_dev(who, gt, "gt", torch.float32)
+        if gt.dim() != 2 or gt.shape[1] != (7 if lidar else 4):
+            raise _hip.HipError("%s: gt must be (G, %d), got %s" % (who, 7 if lidar else 4, tuple(gt.shape)))
+        num_gt = int(gt.shape[0])
+        _draw_dev(who, gt_labels, "gt_labels", torch.int32, (num_gt,))
+    capacity = draw_plan_capacity(k, max_out, num_gt)
+    rows = _draw_out(who, rows, "rows", torch.int32, (capacity, DRAW_ROW_INTS), dets.device)
+    key_col, key_cols = (0, 0) if key is None else (int(key[0]), int(key[1]))
+    if limiter_resets is None:
+        limiter_resets = not lidar
+    if capacity == 0:
+        return rows
+    _hip.check(_hip.load().frcnn_draw_plan(_ptr(dets), _ptr(counts), k, max_out, elem, int(bool(lidar)), key_col, key_cols,
+                                           int(limiter0), int(bool(limiter_resets)), _ptr(gt) if num_gt else None,
+                                           _ptr(gt_labels) if num_gt else None, num_gt, int(canvas_hw[0]),
+                                           int(canvas_hw[1]), _ptr(rows), capacity, _stream()), "frcnn_draw_plan")
+    return rows
+
+
+def draw_boxes(canvas, rows, owner=None):
+    """Paint a draw list onto ``canvas`` (H, W, 3) uint8 in place, in exact painter's order (frcnn_draw_scatter +
+    frcnn_draw_compose): row i beats every row before it wherever their outlines cross, whatever the scheduling.
+    ``rows``: int32 (N, DRAW_ROW_INTS); ``owner``: optional (H, W) int32 scratch plane.  Returns ``canvas``."""
+    who = "draw_boxes"
+    _draw_dev(who, canvas, "canvas", torch.uint8)
+    if canvas.dim() != 3 or canvas.shape[2] != 3:
+        raise _hip.HipError("%s: canvas must be (H, W, 3), got %s" % (who, tuple(canvas.shape)))
+    h, w = int(canvas.shape[0]), int(canvas.shape[1])
+    _draw_dev(who, rows, "rows", torch.int32)
+    if rows.dim() != 2 or rows.shape[1] != DRAW_ROW_INTS:
+        raise _hip.HipError("%s: rows must be (N, %d), got %s" % (who, DRAW_ROW_INTS, tuple(rows.shape)))
+    n = int(rows.shape[0])
+    owner = _draw_out(who, owner, "owner", torch.int32, (h, w), canvas.device)
+    lib = _hip.load()
+    _hip.check(lib.frcnn_draw_scatter(_ptr(rows) if n else None, n, _ptr(owner), h, w, _stream()), "frcnn_draw_scatter")
+    _hip.check(lib.frcnn_draw_compose(_ptr(rows) if n else None, n, _ptr(owner), _ptr(canvas), h, w, _stream()),
+               "frcnn_draw_compose")
+    return canvas

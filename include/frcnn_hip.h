@@ -1097,6 +1097,90 @@ int frcnn_sgd_update(float* grad_flat, float* momentum_flat, int64_t flat_elems,
                      const frcnn_sgd_segment* segments_host, int num_segments, const int* chunks_dev, int64_t num_chunks,
                      float momentum, float clip, int zero_grads, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Drawing a frame's detections (version 126; model/test.test_net(draw_det=True), model/draw.render_frame).  Replaces the
+ * Pillow / numpy drawing of the reference's draw_and_save_eval (lib/datasets/waymo_imdb.py:190-253, waymo_lidb.py:229-328,
+ * kitti_lidb.py:289-378) called at lib/model/test.py:231-242.  Every value that decides a byte is formed in float64 or in
+ * integers, one rounding per operation: the outputs are pure functions of the inputs (tests/draw_restatement.py restates
+ * them in numpy, bit for bit).  Launches on `stream` only: no host synchronisation, no float atomics, no memset / memcpy
+ * nodes - a stream capture holds kernel nodes only.
+ *
+ * frcnn_canvas_from_image_blob (waymo_imdb.py:200-204): blob (1, height, width, 3) fp32 -> canvas (height, width, 3) uint8,
+ *   canvas[y][x][o] = byte((double)blob[y][x][c] * stds_host[c] + means_host[c]) with c = arrange_host[o]
+ *   (cfg.PIXEL_STDDEVS, cfg.PIXEL_MEANS, cfg.PIXEL_ARRANGE_BGR).  byte() truncates toward zero like astype(uint8)
+ *   (254.99999 -> 254) and - a stated deviation, numpy's out-of-range cast being undefined - saturates to [0, 255], NaN -> 0.
+ *
+ * frcnn_canvas_from_bev_blob: blob (1, ny, nx, channels) fp32 BEV voxel grid (num_slices height slices, then density, then
+ *   intensity) -> canvas (ny, nx, 3) uint8.  The blob is only read.  With height(cell) = max over the slices:
+ *   FRCNN_DRAW_BEV_KITTI (kitti_lidb.py:289-297, also CADC's): R = height * (255 / (max height - min height)),
+ *     G = density * (255 / max density), B = intensity * (255 / max intensity);
+ *   FRCNN_DRAW_BEV_WAYMO (waymo_lidb.py:240-261): slice i of a cell counts as v + i*0.5 where |v| > 1e-5 (formed on the fly:
+ *     the reference adds it to the blob in place), mask = |height| > 1e-5, max = 1.5 * max(mask * height),
+ *     min = min(mask * height), R = mask * height * (255 / (max - min)), G = density * (6*255 / max density),
+ *     B = intensity * (2*255 / max intensity).
+ *   Three launches: per-workgroup extrema, their finish (the three factors), the colouring; extrema do not depend on the
+ *   order of reduction.  A NaN slice is ignored by the extrema.  Stated deviations: a channel whose range is empty
+ *   (max == min, or max == 0) is written as 0 (the reference divides by zero); values are saturated to [0, 255] before
+ *   the cast (the reference's green channel reaches 1530 and relies on an undefined cast); the arithmetic is float64
+ *   throughout (the reference mixes float32 and float64 by numpy's promotion rules of the day).
+ *   Workspace: frcnn_canvas_from_bev_blob_ws_bytes(), 8-byte aligned.
+ *
+ * frcnn_draw_plan: the device record of a frame -> a draw list in painter's order.  dets (num_classes, max_out, elem) fp32
+ *   rows [x1,y1,x2,y2,score,uncertainty...] (lidar == 0) or [xc,yc,zc,l,w,h,ry,score,uncertainty...] in voxel-grid units
+ *   (lidar != 0), counts (num_classes) int32, as frcnn_filter_per_class* and frcnn_uncertainty_columns leave them;
+ *   gt (num_gt, 4 or 7) fp32 with gt_labels (num_gt) int32 (may be NULL with num_gt == 0).  rows: `capacity` >=
+ *   (num_classes - 1) * max_out + num_gt rows of FRCNN_DRAW_ROW_INTS int32:
+ *     [kind, line width, sequence number, r | g << 8 | b << 16, g0 .. g7]
+ *   FRCNN_DRAW_RECT: g0..g3 = x0,y0,x1,y1 (the float corners truncated toward zero as Pillow's ImageDraw.rectangle
+ *   converts them, pinned to +-2^30); FRCNN_DRAW_FOOTPRINT: g0..g7 = x,y of the four corners of bbox_3d_to_bev_4pt /
+ *   rotate_in_bev (lib/utils/bbox.py:174-233; float64, rounded to float32 like rotate_in_bev's result), clipped to
+ *   [0, canvas_w - 1] x [0, canvas_h - 1] and truncated (draw_bev_bboxes, :346-351); FRCNN_DRAW_SKIP: nothing is drawn
+ *   (a row with a NaN coordinate, and every row behind the last one).  Row i has sequence number i.
+ *   Order: image frames - per class j >= 1 its detections, then the ground truth (waymo_imdb.py:211-251); LiDAR frames -
+ *   the ground truth, then the detections (waymo_lidb.py:268-302).  Inside a class the detections are ordered by
+ *   np.argsort(-key) (db.py:283-303), key = mean of the row's columns key_col .. key_col + key_cols - 1 (fp32 sum in
+ *   column order / count: _normalize_uncertainties, :260-281); key_cols == 0: key = row index, i.e. reverse row order.
+ *   NaN keys last; ties go to the lower row (numpy's default argsort is not stable: the tie rule is this library's).
+ *   Colours: detections (0, (int)(score * 255.0f), (int)((limiter - i) / limiter * 255.0)), i the position in the class's
+ *   order, limiter starting at limiter0 and carried from class to class: a class with 0 < n < limiter detections sets
+ *   limiter = n, any other non-empty class resets it to limiter0 when limiter_resets != 0 (waymo_imdb.py:220-223) and
+ *   leaves it otherwise (waymo_lidb.py:294-295); each component clamped to [0, 255] like Pillow; width 2.  Ground truth:
+ *   image 0 / 255 for label 0 / other, width 1 (waymo_imdb.py:246-251); LiDAR 127 / 255, width 2 (waymo_lidb.py:277-282).
+ *   max_out <= 4096.  One launch.
+ *
+ * frcnn_draw_scatter: owner (height, width) uint32 is cleared by the library's fill kernel, then every outline pixel of row
+ *   i does atomicMax(owner, i + 1): exact painter's order whatever the scheduling.
+ *     FRCNN_DRAW_RECT of width w: the pixels of [x0,x1] x [y0,y1] within w pixels of the rectangle's border, clipped to
+ *     the canvas; empty when x1 < x0 or y1 < y0.  For boxes at least 2w wide and high this is Pillow's
+ *     ImageDraw.rectangle(outline=, width=w); for thinner and degenerate boxes Pillow has quirks (a zero-size box of
+ *     width 2 paints 3x4 pixels) and this rule stands.
+ *     FRCNN_DRAW_FOOTPRINT: the four edges corner i -> corner i-1 (draw_polygon, lib/utils/bbox.py:364-379).  With
+ *     dx = |xb - xa|, dy = |yb - ya|, x the major axis iff dx > dy: for t = 0..dmaj the pixel major_a + s_major * t,
+ *     minor_a + s_minor * ((2*t*dmin + dmaj) / (2*dmaj)) in integer division (a zero-length edge: its one pixel) - the
+ *     closed form of Pillow's ImageDraw.line(width=1), equal to it pixel for pixel in all eight octants
+ *     (tests/test_draw_host.py).  Width 2 also paints the neighbour at +1 along the minor axis, clipped (width w: the
+ *     neighbours at +1 .. +w-1; a footprint row with w > 16 or a corner beyond +-2^20 is not drawn).  PARITY
+ *     UNPINNED for width 2: the reference asks Pillow for width=2 lines, which Pillow fills as polygons.
+ * frcnn_draw_compose: canvas[pixel] = rgb of row owner - 1 where owner != 0.  rows / num_rows as given to
+ *   frcnn_draw_scatter. */
+#define FRCNN_DRAW_ROW_INTS 12
+#define FRCNN_DRAW_SKIP 0
+#define FRCNN_DRAW_RECT 1
+#define FRCNN_DRAW_FOOTPRINT 2
+#define FRCNN_DRAW_BEV_WAYMO 0
+#define FRCNN_DRAW_BEV_KITTI 1
+int frcnn_canvas_from_image_blob(const float* blob, int height, int width, const double* stds_host,
+                                 const double* means_host, const int* arrange_host, uint8_t* canvas, void* stream);
+size_t frcnn_canvas_from_bev_blob_ws_bytes(void);
+int frcnn_canvas_from_bev_blob(const float* blob, int ny, int nx, int channels, int num_slices, int form, uint8_t* canvas,
+                               void* ws, size_t ws_bytes, void* stream);
+int frcnn_draw_plan(const float* dets, const int* counts, int num_classes, int max_out, int elem, int lidar, int key_col,
+                    int key_cols, int limiter0, int limiter_resets, const float* gt, const int* gt_labels, int num_gt,
+                    int canvas_h, int canvas_w, int* rows, int capacity, void* stream);
+int frcnn_draw_scatter(const int* rows, int num_rows, uint32_t* owner, int height, int width, void* stream);
+int frcnn_draw_compose(const int* rows, int num_rows, const uint32_t* owner, uint8_t* canvas, int height, int width,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
