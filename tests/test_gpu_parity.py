@@ -817,8 +817,9 @@ def test_head_fc_softmax_decode(hip):
 @pytest.mark.parametrize("r,variant", [(300, 0), (300, 1), (1024, 0), (1500, 0), (37, 0)])
 @pytest.mark.parametrize("thresh,max_dets", [(0.1, 100), (0.5, 100), (0.05, 20), (0.999, 100)])
 def test_filter_per_class_matches_oracle(hip, thresh, max_dets, r, variant, nms_at_equal):
-    """variant 0: LDS-resident kernel for r <= 1024 (rank sort, wave-per-word ballot matrix), the general workspace kernel
-    above that; variant 1 forces the general kernel.  Both must reproduce the oracle's rows exactly."""
+    """variant 0: LDS-resident kernel for r <= 960, the sizes whose matrix fits its 150 KiB of LDS (rank sort, wave-per-word
+    ballot matrix; here r = 37 and 300), the general workspace kernel above that (r = 1024 and 1500; the switch itself is
+    tested in test_index_edges.py); variant 1 forces the general kernel.  Both must reproduce the oracle's rows exactly."""
     from faster_rcnn_pytorch_multimodal_amd.utils.filter_predictions import filter_device
     g = torch.Generator().manual_seed(int(thresh * 1000) + max_dets)
     k = 3
