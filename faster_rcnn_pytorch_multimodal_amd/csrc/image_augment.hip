@@ -12,6 +12,9 @@
 //   * GAUSS (:567): separable, 5 / 7 / 9 normalised taps computed by the caller in double and passed as fp32 (no expf
 //     here); horizontal pass then vertical pass, each acc = t0*p0, acc += tk*pk in tap order, fp32, no rounding between
 //     the passes; border reflect-101.
+//   * reflect-101 everywhere means np.pad(mode='reflect') for ANY frame dimension n >= 1: the index is folded with
+//     period 2n - 2, so a dimension no larger than the halo (n <= 4 under 9 taps) reflects as often as it takes, and
+//     n == 1 repeats the only sample.
 //   * AVERAGE (:568): k = 2 or 3, integer window sum, round-half-even of sum / k^2; the window of k = 2 covers
 //     offsets {-1, 0} (cv2's anchor k / 2); border reflect-101.
 //   * MEDIAN (:569): 3x3 per channel, border replicate; exchange network on integers (sort the three columns, then
@@ -60,10 +63,14 @@ struct StageParams {
   float p[FRCNN_IMG_NUM_PARAMS];
 };
 
+// BORDER_REFLECT_101 (np.pad mode='reflect') for any n >= 1 and any i: the pattern 0 1 .. n-1 n-2 .. 1 has period 2n - 2
+// and is even about 0, so a halo wider than the frame folds as often as it takes.  n == 1: the only sample.
 __device__ __forceinline__ int reflect101(int i, int n) {
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * n - 2 - i;
-  return min(max(i, 0), n - 1);
+  if ((unsigned)i < (unsigned)n) return i;
+  if (n == 1) return 0;
+  const int period = 2 * n - 2;
+  i = (i < 0 ? -i : i) % period;
+  return i < n ? i : period - i;
 }
 __device__ __forceinline__ uint8_t to_u8(float v) { return (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f); }
 __device__ __forceinline__ int med3i(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }
@@ -333,6 +340,12 @@ extern "C" int frcnn_image_augment(const uint8_t* img_hwc3, int h, int w, int fl
     const float* p = stage_params_host + (size_t)k * FRCNN_IMG_NUM_PARAMS;
     for (int j = 0; j < FRCNN_IMG_NUM_PARAMS; ++j) s.p[j] = p[j];
     FRCNN_REQUIRE(finite_all(p, FRCNN_IMG_NUM_PARAMS), "image_augment: stage %d has a non-finite parameter", k);
+    // a stencil stage launches one row of workgroups per TILE_H frame rows (grid y <= 65535, the rule of image_spatter);
+    // the pointwise stages run on a capped 1-D grid and take any admitted frame
+    if (s.code == FRCNN_IMG_GAUSS || s.code == FRCNN_IMG_AVERAGE || s.code == FRCNN_IMG_MEDIAN || s.code == FRCNN_IMG_SHARPEN)
+      FRCNN_REQUIRE((h + TILE_H - 1) / TILE_H <= 65535,
+                    "image_augment: stage %d: bad frame size %d x %d for a stencil stage (at most %d rows)", k, h, w,
+                    65535 * TILE_H);
     switch (s.code) {
       case FRCNN_IMG_GAUSS:
         FRCNN_REQUIRE(p[0] == 5.f || p[0] == 7.f || p[0] == 9.f, "image_augment: stage %d: gaussian taps must be 5, 7 or 9", k);

@@ -680,6 +680,11 @@ int frcnn_lidar_augment_fov(const float* points, int num_points, int point_strid
  * Draws are counter-based, value = f(seed + *seed_dev, stream, index) (csrc/rng.h; seed_dev device uint32 or NULL).
  * num_stages == 0: a (mirrored) copy.  scratch (frcnn_image_augment_ws_bytes(h, w) bytes, device) is the ping-pong buffer,
  * read only when num_stages > 1 (may be NULL otherwise).  img, out and scratch must not overlap one another: rejected.
+ * Frame size: h, w > 0 and h * w <= 2^29.  A call that holds a stencil stage (GAUSS, AVERAGE, MEDIAN, SHARPEN) further
+ * needs h <= 16 * 65535 = 1048560 (one row of workgroups per 16 frame rows, the rule of frcnn_image_spatter with its own
+ * tile height): a taller frame is rejected with FRCNN_ERR_ARG before anything is launched.  Calls that hold only the
+ * pointwise stages (flip / copy, NOISE, HUE_SAT, AFFINE, DROPOUT) take every admitted size.  The stencil borders are
+ * true reflect-101 (replicate for MEDIAN) for every dimension >= 1, also those no larger than the halo.
  * debug_pre (device, h*w*3 floats, usually NULL): with exactly one NOISE or HUE_SAT stage, the values before rounding.
  * No allocation, no host synchronisation; kernel launches only, so a stream capture holds kernel nodes.
  * Operators restated from the published algorithms of imgaug / cv2 / scikit-image (absent: parity unpinned); the
