@@ -21,6 +21,7 @@ PROTOTYPES = {
     "frcnn_conv2d_fwd_ws_bytes": (c_size_t, [c_int] * 10),
     "frcnn_conv2d_fwd": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 11 + [_P, c_size_t, _P]),
     "frcnn_conv2d_fwd_pre": (c_int, [_P, _P, _P, _P, _P, _P, _P] + [c_int] * 11 + [_P, c_size_t, _P]),
+    "frcnn_conv2d_fwd_wres_pre": (c_int, [_P, _P, _P, _P, _P, _P, _P] + [c_int] * 11 + [_P, c_size_t, _P]),
     "frcnn_conv2d_winograd_filter_bytes": (c_size_t, [c_int, c_int]),
     "frcnn_conv2d_winograd_rows": (c_long, [c_int, c_int, c_int, POINTER(c_long)]),
     "frcnn_conv2d_winograd_filter": (c_int, [_P, _P, c_int, c_int, _P]),

@@ -152,7 +152,7 @@ ConvArgs make_conv_params(const float* x, const float* wgt, const float* scale, 
 int run_conv(const float* x, const float* wgt, const float* scale, const float* shift, const float* residual, float* y, int n,
              int h, int w, int c, int k, int r, int s, int stride, int pad, int relu, int split_k, void* ws, size_t ws_bytes,
              hipStream_t stream, int out_stride, int hy, int wy, const float* u_pre = nullptr, const float* mask = nullptr,
-             const float* mscale = nullptr);
+             const float* mscale = nullptr, bool wino_res = false);
 
 }  // namespace conv
 }  // namespace frcnn

@@ -473,7 +473,7 @@ bool tune_plan(const ConvArgs& p, long M, int k, const float* scale, const float
 int frcnn::conv::run_conv(const float* x, const float* wgt, const float* scale, const float* shift, const float* residual,
                           float* y, int n, int h, int w, int c, int k, int r, int s, int stride, int pad, int relu, int split_k,
                           void* ws, size_t ws_bytes, hipStream_t stream, int out_stride, int hy, int wy, const float* u_pre,
-                          const float* mask, const float* mscale) {
+                          const float* mask, const float* mscale, bool wino_res) {
   ConvArgs p = make_conv_params(x, wgt, scale, shift, residual, y, n, h, w, c, k, r, s, stride, pad, relu);
   p.u_pre = u_pre;
   p.mask = mask;
@@ -492,9 +492,13 @@ int frcnn::conv::run_conv(const float* x, const float* wgt, const float* scale, 
   Plan pl;
   bool have = false;
   if (split_k <= 0 && g_force_tm == 0) {   // cached plans always apply; new shapes are tuned only in autotune mode
-    const ShapeKey key = shape_key(n, h, w, c, k, r, s, stride, pad, out_stride, residual != nullptr);
+    // wino_res (frcnn_conv2d_fwd_wres_pre): the call is planned - looked up, and tuned where a new shape is - as the
+    // residual-free call of its shape; a Winograd plan then runs with the residual in its output transform, and any other
+    // plan hands the call to the ordinary residual route below
+    const bool keyed_res = residual != nullptr && !wino_res;
+    const ShapeKey key = shape_key(n, h, w, c, k, r, s, stride, pad, out_stride, keyed_res);
     have = lookup_plan(key, &pl);
-    const bool wino = residual == nullptr && winograd_ok(r, s, stride, pad, c, k, out_stride);
+    const bool wino = !keyed_res && winograd_ok(r, s, stride, pad, c, k, out_stride);
     // a cached plan of the other form than this call may use (a residual operand, or a forced mode) is left in the cache
     // for the calls it was tuned for; this call runs the analytic plan
     bool keep_cache = false;
@@ -502,7 +506,9 @@ int frcnn::conv::run_conv(const float* x, const float* wgt, const float* scale, 
       have = false;
       keep_cache = true;
     }
-    if (!have && !keep_cache && g_autotune && tune_plan(p, M, k, scale, shift, residual, y, relu, ws, ws_bytes, stream, allow_split, wino, &pl)) {
+    ConvArgs pt = p;                       // what the tuner times: for a wino_res call the residual-free call itself
+    if (!keyed_res) pt.res = nullptr;
+    if (!have && !keep_cache && g_autotune && tune_plan(pt, M, k, scale, shift, pt.res, y, relu, ws, ws_bytes, stream, allow_split, wino, &pl)) {
       std::lock_guard<std::mutex> lock(g_plan_mutex);
       g_plan_cache[key] = pl;
       have = true;
@@ -510,13 +516,16 @@ int frcnn::conv::run_conv(const float* x, const float* wgt, const float* scale, 
   }
   if (!have) {
     pl = choose_plan(p.M, k, p.ksteps, allow_split ? split_k : 1);
-    if (g_algo_mode == 2 && split_k <= 0 && g_force_tm == 0 && residual == nullptr &&
+    if (g_algo_mode == 2 && split_k <= 0 && g_force_tm == 0 && (residual == nullptr || wino_res) &&
         winograd_ok(r, s, stride, pad, c, k, out_stride)) {
       pl = Plan{M >= 2048 ? kTile128x128 : kTile64x64, 1, (c + BK - 1) / BK};   // forced Winograd without tuning: a mid-size GEMM tile
       pl.algo = 1;
       if (g_wino_fuse == 2 && (c % BK) == 0) { pl.cfg = kTile64x64; pl.fuse_in = 1; }
     }
   }
+  if (wino_res && pl.algo != 1)   // the residual-free call would not run Winograd: this is the ordinary call with a residual
+    return run_conv(x, wgt, scale, shift, residual, y, n, h, w, c, k, r, s, stride, pad, relu, split_k, ws, ws_bytes, stream,
+                    out_stride, hy, wy, u_pre, mask, mscale, false);
   if (!have && split_k <= 0 && pl.splits > 1 && (!ws || ws_bytes < plan_ws_bytes(pl, p, M, k))) {
     // the workspace was sized for this shape's cached plan, which does not apply to THIS call (a Winograd plan and a call
     // with a residual): run unsplit rather than fail
@@ -556,6 +565,20 @@ extern "C" int frcnn_conv2d_fwd_pre(const float* x, const float* wgt, const floa
   if (g_prof_on) ++g_prof_call;
   return run_conv(x, wgt, scale, shift, residual, y, n, h, w, c, k, r, s, stride, pad, relu, split_k, ws, ws_bytes,
                   static_cast<hipStream_t>(stream_), 1, 0, 0, w_winograd);
+}
+
+extern "C" int frcnn_conv2d_fwd_wres_pre(const float* x, const float* wgt, const float* w_winograd, const float* scale,
+                                         const float* shift, const float* residual, float* y, int n, int h, int w, int c,
+                                         int k, int r, int s, int stride, int pad, int relu, int split_k, void* ws,
+                                         size_t ws_bytes, void* stream_) {
+  FRCNN_REQUIRE(x && wgt && y, "conv2d_fwd_wres_pre: null tensor (the (k,3,3,c) filter is needed too: the implicit GEMM reads it)");
+  FRCNN_REQUIRE(residual, "conv2d_fwd_wres_pre: null residual (frcnn_conv2d_fwd_pre is the call without one)");
+  FRCNN_REQUIRE(conv_args_ok(n, h, w, c, k, r, s, stride, pad) && winograd_ok(r, s, stride, pad, c, k, 1),
+                "conv2d_fwd_wres_pre: needs a 3x3 / stride 1 / pad 1 layer with c%%4 == 0 and k%%4 == 0 (n=%d h=%d w=%d c=%d k=%d "
+                "r=%d s=%d stride=%d pad=%d)", n, h, w, c, k, r, s, stride, pad);
+  if (g_prof_on) ++g_prof_call;
+  return run_conv(x, wgt, scale, shift, residual, y, n, h, w, c, k, r, s, stride, pad, relu, split_k, ws, ws_bytes,
+                  static_cast<hipStream_t>(stream_), 1, 0, 0, w_winograd, nullptr, nullptr, true);
 }
 
 extern "C" int frcnn_conv2d_profile_begin(void) {

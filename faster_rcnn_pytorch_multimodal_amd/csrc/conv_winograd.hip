@@ -6,7 +6,8 @@
 // rounding error is that of the direct form or smaller (tests/test_gpu_parity.py compares both with float64).
 // Four launches: filter transform (stateless ABI: recomputed per call, 16 KC floats), input transform, ONE grouped
 // launch of the implicit-GEMM kernels as a 1x1 convolution (blockIdx.y = transform component), output transform with
-// the BatchNorm scale / shift and ReLU.  Only the autotuner selects it (choose_plan never does).
+// the BatchNorm scale / shift, (frcnn_conv2d_fwd_wres_pre only) the residual, and ReLU.  Only the autotuner selects it
+// (choose_plan never does).
 //
 // Trimmed components.  A map with odd H has a last tile row whose second output row falls off the map; in Y = A^T M A,
 // A^T = [[1,1,1,0],[0,1,-1,-1]], component row i = 3 feeds nothing but that output row, so the four components (3, j) of
@@ -178,11 +179,16 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
 // y[2ty+a][2tx+b] = act((A^T m A)[a][b] * scale + shift),  A^T = [[1,1,1,0],[0,1,-1,-1]];  one thread per (tile, 4 channels).
 // A component the tile's class lacks is NOT loaded (its rows were never written; the workspace may hold anything): the sums
 // it would enter (s1 of a bottom tile, column 3 of a right one) feed only the outputs dropped below and are left at zero.
+// RES: y = act(v + res) with v = (A^T m A) * scale + shift exactly as without it, ONE rounded add, then the activation - the
+// bits of the residual-free call with relu = 0 followed by a float32 add and a ReLU pass.  res is fp32 NHWC of y's shape and
+// is read at the address the lane stores to, so only where an output exists (partial tiles of odd maps read nothing else).
+template <bool RES>
 __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ Mo, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, float* __restrict__ y, int H,
                                                          int W, int K4, int th, int tw, long T, int relu,
                                                          const float* __restrict__ mask,
-                                                         const float* __restrict__ mscale, const WinoClasses cl) {
+                                                         const float* __restrict__ mscale, const WinoClasses cl,
+                                                         const float* __restrict__ res) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)T * K4) return;
   const int k4 = (int)(idx % K4);
@@ -225,6 +231,7 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
       const int wo = 2 * tx + b;
       if (wo >= W) continue;
       f32x4 v = o[a][b] * sc + sh;
+      if (RES) v = v + reinterpret_cast<const f32x4*>(res)[((size_t)(n * H + ho) * W + wo) * K4 + k4];   // = `at` below
       if (relu) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = frcnn::relu_f32(v[e]);
@@ -287,8 +294,12 @@ int frcnn::conv::launch_winograd(const ConvArgs& p, const Plan& pl, const float*
   }
   rc = launch_gemm(q, gp, g.T, p.K, 16, stream);
   if (rc != FRCNN_OK) return rc;
-  return launch_1d<wino_output_kernel>("wino_output_kernel", (size_t)g.T * (p.K / 4), stream, (const float*)Mo, scale, shift, y,
-                   p.Ho, p.Wo, p.K / 4, g.th, g.tw, g.T, relu, p.mask, p.mscale, g.cl);
+  // p.res: only frcnn_conv2d_fwd_wres_pre plans a call with a residual as Winograd (run_conv)
+  if (p.res)
+    return launch_1d<wino_output_kernel<true>>("wino_output_kernel<res>", (size_t)g.T * (p.K / 4), stream, (const float*)Mo, scale,
+                     shift, y, p.Ho, p.Wo, p.K / 4, g.th, g.tw, g.T, relu, p.mask, p.mscale, g.cl, p.res);
+  return launch_1d<wino_output_kernel<false>>("wino_output_kernel", (size_t)g.T * (p.K / 4), stream, (const float*)Mo, scale, shift, y,
+                   p.Ho, p.Wo, p.K / 4, g.th, g.tw, g.T, relu, p.mask, p.mscale, g.cl, (const float*)nullptr);
 }
 
 extern "C" size_t frcnn_conv2d_winograd_filter_bytes(int k, int c) {

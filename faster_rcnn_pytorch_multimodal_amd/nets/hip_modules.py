@@ -140,8 +140,9 @@ def prepared_conv_concat(owner, cache_name, parts):
     return stable_store(owner, cache_name, key, (w, scale, shift), refresh=lambda: prepared_conv_concat(owner, cache_name, parts))
 
 
-def conv_bn_act(x, conv, bn=None, relu=False, residual=None, use_bn=True):
-    """NHWC in, NHWC out: act(bn(conv(x)) + residual) on the matrix cores (fp32; bf16 operands under cfg.TEST.CONV_BF16)."""
+def conv_bn_act(x, conv, bn=None, relu=False, residual=None, use_bn=True, winograd_residual=False):
+    """NHWC in, NHWC out: act(bn(conv(x)) + residual) on the matrix cores (fp32; bf16 operands under cfg.TEST.CONV_BF16).
+    ``winograd_residual``: see ``conv_forward``."""
     if bn is not None and use_bn and bn.training:
         raise NotImplementedError("BatchNorm in training mode (batch statistics) is not on the HIP path yet")
     w, scale, shift = prepared_conv(conv, bn, use_bn)
@@ -149,7 +150,8 @@ def conv_bn_act(x, conv, bn=None, relu=False, residual=None, use_bn=True):
         x = ops.pad_channels(x, w.shape[-1])
     stride = conv.stride[0] if isinstance(conv.stride, (tuple, list)) else conv.stride
     pad = conv.padding[0] if isinstance(conv.padding, (tuple, list)) else conv.padding
-    return conv_forward(x, w, scale, shift, residual, conv, stride=stride, pad=pad, relu=relu, winograd_of=conv)
+    return conv_forward(x, w, scale, shift, residual, conv, stride=stride, pad=pad, relu=relu, winograd_of=conv,
+                        winograd_residual=winograd_residual)
 
 
 # The mode of the Network.forward in progress ('TRAIN' / 'TEST'): frozen blocks of a training net are in eval() too, so
@@ -231,12 +233,14 @@ def _bf16_entry(holder, name, w_krsc, pack=None):
 
 
 def conv_forward(x, w_krsc, scale, shift, residual, holder, stride=1, pad=0, relu=False, winograd_of=None,
-                 cache_name='_frcnn_bf16'):
+                 cache_name='_frcnn_bf16', winograd_residual=False):
     """The one forward convolution of the inference call sites.  With cfg.TEST.CONV_BF16 in a TEST-mode forward an eligible
     layer (``conv_bf16_eligible``) runs ``ops.conv2d_nhwc_bf16`` on its packed filter, cached on ``holder`` under
     ``cache_name``; after it, with cfg.TEST.CONV_SPLIT_BF16 (default on), a layer the library's rule selects runs the
     fp32-accurate ``ops.conv2d_nhwc_bf16x3`` (filter cached under ``cache_name + 'x3'``); every other call is ``ops.conv2d_nhwc`` exactly as without the switch (``winograd_of``: the module whose
-    pre-transformed Winograd filter a residual-free call may read)."""
+    pre-transformed Winograd filter a residual-free call may read).  ``winograd_residual`` (default off; only
+    ``nets.resnet.BasicBlock`` passes it): a call WITH a residual whose fp32 route is ``ops.conv2d_nhwc_winograd_res``; the
+    bf16 switches come first as everywhere, with the residual in their own epilogue."""
     if conv_bf16_wanted(x, w_krsc, stride, pad):
         return ops.conv2d_nhwc_bf16(x, _bf16_entry(holder, cache_name, w_krsc), scale, shift, residual, stride=stride, pad=pad,
                                     relu=relu)
@@ -244,6 +248,16 @@ def conv_forward(x, w_krsc, scale, shift, residual, holder, stride=1, pad=0, rel
         return ops.conv2d_nhwc_bf16x3(x, _bf16_entry(holder, cache_name + 'x3', w_krsc, ops.conv2d_pack_bf16x3), scale, shift,
                                       residual, stride=stride, pad=pad, relu=relu)
     u = None
+    if winograd_residual:
+        # BasicBlock's closing convolution: planned as the residual-free call of its shape, the residual goes into the
+        # Winograd output transform where that plan is Winograd (ops.conv2d_nhwc_winograd_res); U from the same cache
+        k, r, s, c = w_krsc.shape
+        if residual is None or not ops.winograd_eligible(k, r, s, c, stride, pad):
+            raise ValueError("conv_forward: winograd_residual needs a residual and a 3x3 / stride 1 / pad 1 layer with "
+                             "C % 4 == 0 and K % 4 == 0")
+        if winograd_of is not None:
+            u = _winograd_filter(winograd_of, w_krsc, tuple(x.shape[:3]), stride, pad)
+        return ops.conv2d_nhwc_winograd_res(x, w_krsc, residual, scale, shift, relu=relu, w_winograd=u)
     if winograd_of is not None and residual is None:
         n, h, wd, c = x.shape
         u = _winograd_filter(winograd_of, w_krsc, (n, h, wd), stride, pad)

@@ -6,6 +6,10 @@ stride is 4 and every pyramid level has 256 channels.  ``_layers['head']`` = ste
 (imagenet.py:131-134).  conv1/bn1 and ``layerN`` for N <= cfg.RESNET.FIXED_BLOCKS are frozen, BatchNorm is
 frozen and kept in eval mode unless FIXED_BLOCKS == -1 (imagenet.py:96-116, 138-163) — which is what lets
 every BatchNorm be folded into its convolution's epilogue on the HIP path.
+
+``num_layers`` 18 / 34 (the BasicBlock ResNets, inference only, no FPN, no UC heads): the widths follow the block's expansion
+of 1 - net_conv and the pooled RoIs have 256 channels, layer4 lifts them to 512 (``_fc7_channels``, ``_det_net_channels``) -
+where imagenet.py:47-49 hard-codes the Bottleneck's 1024 / 1024 / 2048.
 """
 import torch
 import torch.nn as nn
@@ -15,6 +19,7 @@ from ..utils.init_utils import const_init, normal_init, set_bn_eval, set_bn_fix,
 from .fpn import fpn
 from . import uncertainty
 from .network import Network
+from .resnet import BASIC_DEPTHS, BASIC_TRAIN_NOT_BUILT
 
 
 class _Head(nn.Module):
@@ -35,6 +40,16 @@ class _Head(nn.Module):
 class imagenet(Network):
     def __init__(self, num_layers=50):
         Network.__init__(self)
+        basic = num_layers in BASIC_DEPTHS
+        if basic:
+            # depth 18 / 34 (tools/trainval_net.py:389-390 offers --net res34): inference without FPN and without the UC heads
+            if cfg.USE_FPN:
+                raise NotImplementedError("cfg.USE_FPN with imagenet(num_layers=%d): the pyramid on the BasicBlock ResNets is "
+                                          "not built (its lateral widths are the Bottleneck's)" % num_layers)
+            uc = [k for k in cfg.UC if k.startswith('EN_') and cfg.UC[k]]
+            if uc:
+                raise NotImplementedError("cfg.UC.%s with imagenet(num_layers=%d): the uncertainty heads are not built on the "
+                                          "BasicBlock ResNets" % (", cfg.UC.".join(uc), num_layers))
         if cfg.USE_FPN:
             if cfg.POOLING_MODE == 'multiscale':
                 self._feat_stride = 4
@@ -46,9 +61,10 @@ class imagenet(Network):
             self._feat_stride = 16
             self._fpn_en = False
             self._batchnorm_en = True
-            self._net_conv_channels = 1024
-            self._roi_pooling_channels = 1024
-        self._fc7_channels = 2048
+            # layer3's width: 256 x the block's expansion (imagenet.py:47-49 hard-codes the Bottleneck's 1024 / 1024 / 2048)
+            self._net_conv_channels = 256 if basic else 1024
+            self._roi_pooling_channels = self._net_conv_channels
+        self._fc7_channels = 512 if basic else 2048
         self.inplanes = 64
         self._num_resnet_layers = num_layers
         # imagenet.py:52-63: with MC dropout the detection heads read fc7 / 4 features (nets/uncertainty.py builds them)
@@ -93,6 +109,12 @@ class imagenet(Network):
                 self._layers['layer%d' % i] = getattr(self.resnet, 'layer%d' % i)
         else:
             self._layers['head'] = _Head(self.resnet)
+
+    def forward(self, image, info, gt_boxes=None, gt_boxes_dc=None, mode='TRAIN'):
+        if mode != 'TEST' and self._num_resnet_layers in BASIC_DEPTHS:
+            raise NotImplementedError("imagenet(num_layers=%d).forward(mode=%r): inference only - %s"
+                                      % (self._num_resnet_layers, mode, BASIC_TRAIN_NOT_BUILT))
+        return Network.forward(self, image, info, gt_boxes, gt_boxes_dc, mode=mode)
 
     def train(self, mode=True):
         nn.Module.train(self, mode)

@@ -23,6 +23,9 @@ from .network import Network
 class lidarnet(Network):
     def __init__(self, num_layers=50):
         Network.__init__(self)
+        if num_layers in (18, 34):
+            raise NotImplementedError("lidarnet(num_layers=%d): the BasicBlock ResNets are built for the image detector only "
+                                      "(nets.imagenet); the LiDAR detector takes depth 50 / 101 / 152" % num_layers)
         if cfg.USE_FPN:
             # lidarnet.py:31-40: same pyramid as the image detector (p2..p5, 256 channels, RPN on p2 at stride 4,
             # multi-scale pooling, custom tail); layer4 is part of the backbone and keeps its BatchNorm

@@ -121,6 +121,9 @@ class Network(nn.Module):
 
     def _build_resnet(self):
         depth = self._num_resnet_layers
+        if depth in custom_resnet.BASIC_DEPTHS:
+            build = custom_resnet.resnet18 if depth == 18 else custom_resnet.resnet34
+            return build(dropout_en=self._dropout_en, drop_rate=self._resnet_drop_rate, batchnorm_en=self._batchnorm_en)
         if depth == 50:
             return custom_resnet.resnet50(dropout_en=self._dropout_en, drop_rate=self._resnet_drop_rate,
                                           batchnorm_en=self._batchnorm_en)

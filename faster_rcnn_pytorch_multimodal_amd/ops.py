@@ -230,6 +230,52 @@ def conv2d_nhwc(x, w_krsc, scale=None, shift=None, residual=None, stride=1, pad=
     return out
 
 
+def conv2d_nhwc_winograd_res(x, w_krsc, residual, scale=None, shift=None, relu=False, out=None, w_winograd=None, ws=None):
+    """y = act((conv3x3(x, w) * scale + shift) + residual) of a 3x3 / stride 1 / pad 1 layer (the closing convolution of a
+    BasicBlock)  —  frcnn_conv2d_fwd_wres_pre: planned as the RESIDUAL-FREE call of its shape; where that plan is Winograd
+    F(2x2, 3x3) the residual is added in the Winograd output transform (bit for bit the residual-free call with relu off, then a
+    float32 add and a ReLU), otherwise the call is ``conv2d_nhwc(..., residual=residual)``.  ``w_winograd``: the pre-transformed
+    filter (``winograd_filter``) or None; ``ws`` (tests): the workspace, frcnn_conv2d_fwd_ws_bytes of it."""
+    lib = _hip.load()
+    _dev_f32(x, "x"); _dev_f32(w_krsc, "w")
+    if x.dim() != 4 or w_krsc.dim() != 4:
+        raise _hip.HipError("conv2d_nhwc_winograd_res: x must be (n,h,w,c) and w (k,3,3,c), got %s and %s"
+                            % (tuple(x.shape), tuple(w_krsc.shape)))
+    n, h, w, c = x.shape
+    k, r, s, c2 = w_krsc.shape
+    if c2 != c:
+        raise _hip.HipError("conv2d_nhwc_winograd_res: input has %d channels, filter expects %d" % (c, c2))
+    if not winograd_eligible(k, r, s, c, 1, 1):
+        raise _hip.HipError("conv2d_nhwc_winograd_res: need a (k,3,3,c) filter with k%%4 == 0 and c%%4 == 0, got %s" % (tuple(w_krsc.shape),))
+    for nm, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _dev_f32(t, nm)
+            if t.numel() != k:
+                raise _hip.HipError("conv2d_nhwc_winograd_res: %s has %d elements, expected %d" % (nm, t.numel(), k))
+    if residual is None:
+        raise _hip.HipError("conv2d_nhwc_winograd_res: residual is None (conv2d_nhwc is the call without one)")
+    _dev_f32(residual, "residual")
+    if tuple(residual.shape) != (n, h, w, k):
+        raise _hip.HipError("conv2d_nhwc_winograd_res: residual shape %s != output shape %s" % (tuple(residual.shape), (n, h, w, k)))
+    out = _given_output("conv2d_nhwc_winograd_res", out, (n, h, w, k), x.device)
+    if w_winograd is not None:
+        _dev_f32(w_winograd, "w_winograd")
+        if tuple(w_winograd.shape) != (16, k, c):
+            raise _hip.HipError("conv2d_nhwc_winograd_res: w_winograd has shape %s, expected %s" % (tuple(w_winograd.shape), (16, k, c)))
+    ws_bytes = lib.frcnn_conv2d_fwd_ws_bytes(n, h, w, c, k, 3, 3, 1, 1, 0)
+    ws = _given_workspace("conv2d_nhwc_winograd_res", ws, ws_bytes, x.device)
+    _hip.check(lib.frcnn_conv2d_fwd_wres_pre(_ptr(x), _ptr(w_krsc), _ptr(w_winograd), _ptr(scale), _ptr(shift), _ptr(residual),
+                                             _ptr(out), n, h, w, c, k, 3, 3, 1, 1, int(bool(relu)), 0, _ptr(ws), ws_bytes,
+                                             _stream()), "frcnn_conv2d_fwd_wres_pre")
+    flops = 2.0 * n * h * w * k * 9 * c
+    if PROFILE is not None:
+        PROFILE.append({"n": n, "h": h, "w": w, "c": c, "k": k, "r": 3, "s": 3, "stride": 1, "pad": 1, "residual": True,
+                        "relu": bool(relu), "flops": flops, "winograd_res": True})
+    if FLOPS is not None:
+        _log_flops('fwd', flops, _CONV_ALGO_MODE != 1 and (_CONV_ALGO_MODE == 2 or conv_plan_algo(n, h, w, c, k, 3, 3, 1, 1, False) == 1))
+    return out
+
+
 def conv2d_pack_bf16(w_krsc):
     """(K,R,S,C) fp32 filter -> the same array as bf16 words (int16 tensor), rounded to nearest even: the filter operand of
     ``conv2d_nhwc_bf16`` (frcnn_conv2d_pack_bf16); constant while the weights are."""

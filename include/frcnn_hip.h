@@ -233,6 +233,21 @@ int frcnn_conv2d_winograd_filter(const float* w_krsc, float* u, int k, int c, vo
 int frcnn_conv2d_fwd_pre(const float* x, const float* w_krsc, const float* w_winograd, const float* scale,
                          const float* shift, const float* residual, float* y, int n, int h, int w, int c, int k, int r,
                          int s, int stride, int pad, int relu, int split_k, void* ws, size_t ws_bytes, void* stream);
+/* The closing convolution of a BasicBlock (lib/nets/resnet.py:62-69: relu(bn2(conv2(out)) + identity), conv2 3x3 / stride 1 /
+ * pad 1) with the residual applied INSIDE a Winograd plan: frcnn_conv2d_fwd keeps its rule that a call with a residual runs
+ * the implicit GEMM; this entry plans the call as the RESIDUAL-FREE call of its shape - the cached (tuned or imported) plan
+ * under the residual-free key, forced Winograd (frcnn_conv2d_set_algo 2), a new shape tuned with autotuning on exactly as the
+ * residual-free call would tune it - and where that plan is a Winograd plan (fused input transform and persistent tile
+ * included) its output transform stores
+ *     y = act( ((A^T m A) * scale + shift) + residual )
+ * with (A^T m A) * scale + shift evaluated as without a residual, one rounded add, then the activation (relu(NaN) = NaN): bit
+ * for bit the residual-free call with relu = 0 followed by a float32 add and a ReLU pass.  Where that plan is not a Winograd plan
+ * (also: split_k > 0, a forced tile) the call IS frcnn_conv2d_fwd_pre with the residual.  Workspace: frcnn_conv2d_fwd_ws_bytes,
+ * as for the residual-free call.  FRCNN_ERR_ARG without a launch: a NULL x / w_krsc / y / residual, and every shape that is not
+ * 3x3 / stride 1 / pad 1 with c % 4 == 0 and k % 4 == 0.  w_winograd may be NULL (the filter is then transformed inside the call). */
+int frcnn_conv2d_fwd_wres_pre(const float* x, const float* w_krsc, const float* w_winograd, const float* scale,
+                              const float* shift, const float* residual, float* y, int n, int h, int w, int c, int k, int r,
+                              int s, int stride, int pad, int relu, int split_k, void* ws, size_t ws_bytes, void* stream);
 
 /* Opt-in inference form of frcnn_conv2d_fwd with bf16 OPERANDS on v_mfma_f32_32x32x16_bf16 (fp32 accumulation):
  *     y = act( (sum bf16(x) * bf16(w)) * scale + shift + residual )
